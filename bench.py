@@ -18,7 +18,10 @@ which a chain spends all but its first step.
 Rank 0 prints ONE JSON line.  `value` is the whole-job rate: steps of all
 chains / max-over-ranks wall time.  Chains are independent (weak scaling, no
 collective in the data path); torch.distributed (gloo) is used only for the
-barrier and the max-reduction of the timings.
+barrier and the max-reduction of the timings.  `--dump-outputs DIR` writes
+what the last timed step recorded as DIR/<name>.npy (dump_outputs); the data
+and the chain's seed are fixed by the arguments, so two builds can be compared
+output for output.
 
 roofline: the cells x clusters x mutations kernel (k_ll) at the workload's
 first-sweep shape, timed live with HIP events on the library's stream; the
@@ -97,6 +100,35 @@ def step(chain, i, burn_in):
     """do_step + update_results: ONE native call on the device model
     (Chain.step -> CRP.native_step), the two calls for the oracle."""
     chain.step(i, i < burn_in)
+
+
+DUMP_LIMIT = 64 << 20       # bytes of --dump-outputs, .npy headers included
+
+
+def dump_outputs(out_dir, results, slot, K):
+    """What the chain's caller receives for step `slot` (its results in the
+    reference's layout), as DIR/<name>.npy in float64 / float32: the scalars
+    ML, MAP, DP_alpha, FN, FP, the cells' cluster labels `assignments` and
+    `params`, the parameter rows of the K populated clusters in ascending
+    cluster id.  `params_rows` lists which of the K rows `params` holds: all
+    of them, or, where they would not fit in DUMP_LIMIT, a fixed seeded sample
+    (drawn from a stream of its own: the chain's is left where it is)."""
+    out = {key: np.array([results[key][slot]], dtype=np.float64)
+        for key in ('ML', 'MAP', 'DP_alpha', 'FN', 'FP')}
+    out['assignments'] = results['assignments'][slot].astype(np.float64)
+    # (the parameter trace holds the post-burn-in slots only, at its end)
+    params = results['params']
+    rows = params[slot - (results['ML'].size - params.shape[0]), :K]
+    keep = np.arange(K)
+    room = DUMP_LIMIT - 4096 - sum(a.nbytes for a in out.values())
+    if rows.nbytes + 8 * K > room:
+        n = room // (4 * rows.shape[1] + 8)
+        keep = np.sort(np.random.RandomState(0).choice(K, n, replace=False))
+    out['params'] = np.ascontiguousarray(rows[keep], dtype=np.float32)
+    out['params_rows'] = keep.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, arr in out.items():
+        np.save(os.path.join(out_dir, name + '.npy'), arr)
 
 
 class MoveClock:
@@ -457,17 +489,24 @@ def main():
             'least one step is made: a warm-up of 0 puts the first sweep, '
             'minutes on the CPU, into the leg)')
     ap.add_argument('--kernel-reps', type=int, default=5)
-    ap.add_argument('--sustained-steps', type=int, default=200,
+    # the two legs after the window time steps of their own: off unless asked
+    # for, so that --steps alone sets how many steps are timed
+    ap.add_argument('--sustained-steps', type=int, default=0,
         help='steps run AFTER the timed window for the line\'s `sustained` '
             'rate (0 = skip); the window itself is untouched')
-    ap.add_argument('--device-steps', type=int, default=50,
+    ap.add_argument('--device-steps', type=int, default=0,
         help='steps run after those with per-launch device timers on, for '
             '`window.device_ms_per_step` (0 = skip)')
+    ap.add_argument('--dump-outputs', metavar='DIR',
+        help='write the state the last timed step recorded (rank 0) as '
+            'DIR/<name>.npy')
     ap.add_argument('--dry', action='store_true',
         help='the rank harness only: no chain, no device (CPU tests)')
     ap.add_argument('--dry-fail-rank', type=int, default=-1,
         help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
 
     # --gpus N means N ranks.  Under a launcher (WORLD_SIZE set) the two must
     # agree; without one this process starts the ranks itself, before any GPU
@@ -538,6 +577,9 @@ def main():
     clock.on = False
     K_end = len(model.cells_per_cluster)
     ml_end = float(chain.results['ML'][total])
+    if args.dump_outputs and rank == 0:
+        # before the legs below walk the chain on
+        dump_outputs(args.dump_outputs, chain.results, total, K_end)
     stats1 = dict(model.host_stats())
     screen1 = model._dev().mh_screen_stats()
     window = clock.report(args.steps, elapsed)      # (this rank's phases)

@@ -147,6 +147,62 @@ def test_bench_command_reports_a_rank_that_fails():
     assert not [ln for ln in res.stdout.splitlines() if ln.startswith('{')]
 
 
+def test_bench_refuses_fewer_than_one_timed_step():
+    res = _bench_cmd(['--gpus', '1', '--steps', '0', '--dry'])
+    assert res.returncode == 2
+    assert '--steps must be at least 1' in res.stderr and not res.stdout
+
+
+def test_bench_dump_outputs_are_the_last_steps_record(monkeypatch, tmp_path):
+    """bench.py --dump-outputs: the recorded state of the chain's last step as
+    float64 / float32 .npy files - labels, parameter rows of the populated
+    clusters, scalars - and, past the size limit, a fixed sample of the
+    parameter rows that leaves the chain's stream alone."""
+    import bench
+    monkeypatch.setattr(_lib, 'Context', FakeContext)
+    data = H.synth(3, 60, 40, 3, 0.2)
+    np.random.seed(5)
+    model = H.make(P, 'learn', data)
+    model.init()
+    steps = 8
+    chain = bench.new_chain(model, True, steps)
+    for i in range(1, steps + 1):
+        bench.step(chain, i, int(steps * .33))
+    res = chain.results
+    live = np.sort(list(model.cells_per_cluster))
+    K = live.size
+
+    def load(d):
+        return {f[:-4]: np.load(os.path.join(d, f)) for f in os.listdir(d)}
+
+    bench.dump_outputs(str(tmp_path / 'all'), res, steps, K)
+    got = load(str(tmp_path / 'all'))
+    assert sorted(got) == ['DP_alpha', 'FN', 'FP', 'MAP', 'ML',
+        'assignments', 'params', 'params_rows']
+    for key in ('ML', 'MAP', 'DP_alpha', 'FN', 'FP'):
+        assert got[key].dtype == np.float64 and got[key][0] == res[key][steps]
+    assert got['assignments'].dtype == np.float64
+    assert np.array_equal(got['assignments'], res['assignments'][steps])
+    assert got['params'].dtype == np.float32
+    assert np.array_equal(got['params'], model.parameters[live])
+    assert np.array_equal(got['params_rows'], np.arange(K))
+
+    # room for two parameter rows only
+    limit = 4096 + 5 * 8 + data.shape[0] * 8 + 2 * (4 * data.shape[1] + 8)
+    monkeypatch.setattr(bench, 'DUMP_LIMIT', limit)
+    state = np.random.get_state()[1].copy()
+    for name in ('a', 'b'):
+        bench.dump_outputs(str(tmp_path / name), res, steps, K)
+    assert np.array_equal(np.random.get_state()[1], state)
+    a, b = load(str(tmp_path / 'a')), load(str(tmp_path / 'b'))
+    rows = a['params_rows'].astype(int)
+    assert rows.size == 2 and np.all(np.diff(rows) > 0) and rows[-1] < K
+    assert np.array_equal(a['params'], model.parameters[live][rows])
+    assert all(np.array_equal(a[k], b[k]) for k in a)
+    assert sum(os.path.getsize(str(tmp_path / 'a' / f))
+        for f in os.listdir(str(tmp_path / 'a'))) <= limit
+
+
 def test_record_targets_follow_the_trace_arrays():
     """TraceStore.record_target (where a natively made step writes what it
     records) caches the arrays' base addresses per SET of arrays: a trace
