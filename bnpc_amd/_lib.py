@@ -291,11 +291,15 @@ SIGNATURES = {
         _pi64, _pd, _pd, _pd, _pi64, _pi64, _pi64, _pi64, _pi64, _pd]),
     'bnpc_parse_matrix': (C.c_int, [C.c_char_p, C.c_char, C.c_int, C.c_int,
         C.c_void_p, _pi64, _pi64]),
+    'bnpc_write_table': (C.c_int, [C.c_char_p, _i64, _i64, C.c_void_p,
+        _pi64, _i64, _pi32]),
     'bnpc_codist': (C.c_int, [C.c_int, _pi32, _i64, _i64, _pi32]),
     'bnpc_post_create': (C.c_int, [C.c_int, _pi32, _i64, _i64,
         C.POINTER(C.c_void_p), C.POINTER(_i64)]),
     'bnpc_post_fetch': (C.c_int, [C.c_void_p, _pi32, _pd]),
     'bnpc_post_mpear': (C.c_int, [C.c_void_p, C.c_void_p, _i64, _pi64]),
+    'bnpc_post_genotypes': (C.c_int, [C.c_void_p, _pi32, _i64, _pf, _i64,
+        _i64, _i64, _pd]),
     'bnpc_post_ward': (C.c_int, [C.c_void_p, _pd]),
     'bnpc_post_ward_stats': (C.c_int, [C.c_void_p, C.POINTER(_i64),
         C.POINTER(_i64)]),
@@ -695,6 +699,23 @@ class Posterior:
             part = np.ascontiguousarray(lab[c0:c0 + 1024])
             check(load().bnpc_post_mpear(self._h, ptr(part),
                 part.shape[0], ptr(out[c0:])), 'post_mpear')
+        return out
+
+    def genotypes(self, labels, params, chunk=0):
+        """The per-cluster mean parameters of utils.py:148-192 (bnpc_post_
+        genotypes): labels, the MPEAR cluster of every cell, compact in
+        [0, K); params: the samples x W x M parameter trace (float32 draws;
+        float64 padding converts losslessly).  -> float64 (K, M).  chunk:
+        samples per upload (0: about 512 MB)."""
+        lab = np.ascontiguousarray(labels, dtype=np.int32)
+        assert lab.shape == (self.N,)
+        par = np.ascontiguousarray(params, dtype=np.float32)
+        assert par.ndim == 3 and par.shape[0] == self.S
+        K = int(lab.max()) + 1 if lab.size else 0
+        out = np.empty((max(K, 0), par.shape[2]), dtype=np.float64)
+        check(load().bnpc_post_genotypes(self._h, ptr(lab), K, ptr(par),
+            par.shape[1], par.shape[2], int(chunk), ptr(out)),
+            'post_genotypes')
         return out
 
     def close(self):

@@ -16,6 +16,7 @@
 #include <stdint.h>
 #include <string.h>
 #include <algorithm>
+#include <vector>
 
 #include "bnpc_hip.h"
 #include "bnpc_internal.h"
@@ -236,6 +237,8 @@ struct bnpc_post {
     int device = 0;
     int64_t S = 0, N = 0;
     int *differ = nullptr;                  // condensed, device
+    int *assign = nullptr;                  // the S x N samples, device
+    bool labels_in_range = false;           // every sample label in [0, N)
     unsigned long long *sums = nullptr;     // device scratch
     long long ward_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};       // row scans / chain steps of the
                                             // last bnpc_post_ward
@@ -268,6 +271,7 @@ extern "C" int bnpc_post_destroy(bnpc_post *p)
     if (!p) return 0;
     (void)hipSetDevice(p->device);
     if (p->differ) (void)hipFree(p->differ);
+    if (p->assign) (void)hipFree(p->assign);
     if (p->sums) (void)hipFree(p->sums);
     delete p;
     return 0;
@@ -315,9 +319,19 @@ extern "C" int bnpc_post_create(int device, const int32_t *assignments,
     hipLaunchKernelGGL(k_differ_sum, dim3(1024), dim3(256), 0, 0, p->differ,
                        (long long)pairs, p->sums);
     PF(hipGetLastError());
+    // the samples stay on the device for bnpc_post_genotypes, which indexes
+    // with their labels: the range is checked here, on the host
+    int lo = 0, hi = 0;
+    const size_t total_labels = (size_t)S * N;
+    if (total_labels) lo = hi = assignments[0];
+    for (size_t i = 0; i < total_labels; i++) {
+        lo = std::min(lo, assignments[i]);
+        hi = std::max(hi, assignments[i]);
+    }
+    p->labels_in_range = lo >= 0 && (int64_t)hi < N;
     unsigned long long total = 0;
     PF(hipMemcpy(&total, p->sums, sizeof total, hipMemcpyDeviceToHost));
-    (void)hipFree(d_a);
+    p->assign = d_a;
     d_a = nullptr;
 #undef PF
     if (differ_sum) *differ_sum = (int64_t)total;
@@ -963,5 +977,485 @@ extern "C" int bnpc_post_ward(bnpc_post *p, double *Z_raw)
                        "(non-finite distances?)");
         return 1;
     }
+    return 0;
+}
+
+// ---------------------------------------------------------------------------
+// Posterior genotypes (utils.py:148-192): per MPEAR cluster k, the mean of
+// the sampled parameter rows of the samples in which k's cells sit together
+// (and alone, if such samples exist); a cluster that is never together takes
+// the count-weighted rows of the labels its cells carry, over every sample.
+//
+// Read closely, the reference's loop needs, per (cluster, sample):
+//   together  all of k's labels equal (the `bincount` argmax is then that
+//             common label c; where k is not together it is never used)
+//   alone     no cell outside k carries c
+//   rank      the row of c in params_full[s]: the distinct labels of sample s
+//             below c
+// Pass 1 (k_gt_flags, one workgroup per sample) reads the sample row once:
+// a presence bitmap of its labels with per-word prefix popcounts (rank), a
+// label -> owning cluster map written twice with plain stores (any member's
+// cluster, then MIXED wherever a member disagrees), and per cluster one
+// member's label, marked bad wherever another member disagrees.  Nothing is
+// ordered, so nothing needs an atomic but the bitmap's OR.
+// Pass 1b (k_gt_hist, only for clusters never together): per sample the
+// (rank, count) histogram of the cluster's labels, in rank order.
+// Pass 2 (k_gt_accum, one thread per (cluster, mutation)) walks the chosen
+// samples in increasing s with a float64 accumulator, exactly the
+// reference's `params[row] += params_full[s][rank]`; for a never-together
+// cluster each sample's term is summed in rank order from 0 (`np.dot` of
+// integer counts: every product is exact) and then added.  The parameter
+// trace is streamed in sample chunks; the accumulators stay on the device.
+// The divisions are the host's.
+//
+// The pass-1 working set (2.25 N bytes + 8 K) sits in LDS while it fits
+// (about 70 000 cells); past that each workgroup takes a slice of global
+// memory and the same code runs on it through flat pointers.
+// ---------------------------------------------------------------------------
+#define GT_MIXED 0xfffeu
+#define GT_LDS_MAX 163840
+#define GT_GLOBAL_WG 512
+
+// exclusive prefix popcount of nw bitmap words (all threads call); the
+// distinct labels in total are returned to every thread
+__device__ static unsigned gt_scan(const unsigned *bm, unsigned *pf,
+                                   long long nw, unsigned *part)
+{
+    const int tid = threadIdx.x;
+    const long long per = (nw + 255) / 256;
+    const long long w0 = std::min(nw, tid * per), w1 = std::min(nw, w0 + per);
+    unsigned sum = 0;
+    for (long long w = w0; w < w1; w++) sum += __popc(bm[w]);
+    part[tid] = sum;
+    __syncthreads();
+    if (tid == 0) {
+        unsigned run = 0;
+        for (int t = 0; t < 256; t++) {
+            const unsigned v = part[t];
+            part[t] = run;
+            run += v;
+        }
+        part[256] = run;
+    }
+    __syncthreads();
+    unsigned run = part[tid];
+    for (long long w = w0; w < w1; w++) {
+        pf[w] = run;
+        run += __popc(bm[w]);
+    }
+    const unsigned total = part[256];
+    __syncthreads();                        // part is reused by the next scan
+    return total;
+}
+
+__device__ static inline unsigned gt_rank(const unsigned *bm,
+                                          const unsigned *pf, int L)
+{
+    return pf[L >> 5] + __popc(bm[L >> 5] & ((1u << (L & 31)) - 1u));
+}
+
+// pass-1 working set in 32-bit words: part[260] bm[nw] pf[nw] own[N] (uint16)
+// rep[K] bad[K]
+static long long gt_flags_words(long long N, long long K)
+{
+    const long long nw = (N + 31) / 32;
+    return 260 + 2 * nw + (N + 1) / 2 + 2 * K;
+}
+
+__global__ __launch_bounds__(256) void k_gt_flags(
+    const int *__restrict__ a, long long S, long long N,
+    const unsigned short *__restrict__ cl, int K,
+    unsigned *gscratch, long long stride,
+    unsigned char *__restrict__ flags,      // [K][S]: 1 together, 2 alone
+    int *__restrict__ rank,                 // [K][S]
+    int *__restrict__ distinct)             // [S]
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned gt_lds[];
+    unsigned *area = gscratch ? gscratch + blockIdx.x * stride : gt_lds;
+    const long long nw = (N + 31) / 32;
+    unsigned *part = area;
+    unsigned *bm = area + 260;
+    unsigned *pf = bm + nw;
+    unsigned short *own = (unsigned short *)(pf + nw);
+    int *rep = (int *)(pf + nw + (N + 1) / 2);
+    unsigned *bad = (unsigned *)(rep + K);
+    const int tid = threadIdx.x;
+    for (long long s = blockIdx.x; s < S; s += gridDim.x) {
+        const int *row = a + s * N;
+        for (long long w = tid; w < nw; w += 256) bm[w] = 0;
+        for (int k = tid; k < K; k += 256) bad[k] = 0;
+        __syncthreads();
+        for (long long i = tid; i < N; i += 256) {
+            const int L = row[i];
+            const unsigned short k = cl[i];
+            atomicOr(&bm[L >> 5], 1u << (L & 31));
+            own[L] = k;
+            rep[k] = L;
+        }
+        __syncthreads();
+        for (long long i = tid; i < N; i += 256) {
+            const int L = row[i];
+            const unsigned short k = cl[i];
+            if (own[L] != k) own[L] = (unsigned short)GT_MIXED;
+            if (rep[k] != L) bad[k] = 1;
+        }
+        __syncthreads();
+        const unsigned total = gt_scan(bm, pf, nw, part);
+        for (int k = tid; k < K; k += 256) {
+            const int c = rep[k];
+            const bool together = bad[k] == 0;
+            const bool alone = together && own[c] == (unsigned short)k;
+            flags[(size_t)k * S + s] =
+                (unsigned char)((together ? 1 : 0) | (alone ? 2 : 0));
+            rank[(size_t)k * S + s] = (int)gt_rank(bm, pf, c);
+        }
+        if (tid == 0) distinct[s] = (int)total;
+        __syncthreads();                    // the area is reused
+    }
+}
+
+// pass-1b working set in 32-bit words: part[260] bm[nw] pf[nw] lb[nw] lp[nw]
+static long long gt_hist_words(long long N)
+{
+    return 260 + 4 * ((N + 31) / 32);
+}
+
+// per sample and never-together cluster j (cells members[mstart[j] ..
+// + msize[j]]): hd[j][s] distinct labels, then hcnt / hrank[hbase[j] +
+// s * msize[j] + q] the count and the sample rank of its q-th smallest label
+__global__ __launch_bounds__(256) void k_gt_hist(
+    const int *__restrict__ a, long long S, long long N,
+    const int *__restrict__ members, const long long *__restrict__ mstart,
+    const int *__restrict__ msize, const long long *__restrict__ hbase,
+    int NT, unsigned *gscratch, long long stride,
+    int *__restrict__ hcnt, int *__restrict__ hrank, int *__restrict__ hd)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned gt_lds[];
+    unsigned *area = gscratch ? gscratch + blockIdx.x * stride : gt_lds;
+    const long long nw = (N + 31) / 32;
+    unsigned *part = area;
+    unsigned *bm = area + 260;
+    unsigned *pf = bm + nw;
+    unsigned *lb = pf + nw;
+    unsigned *lp = lb + nw;
+    const int tid = threadIdx.x;
+    for (long long s = blockIdx.x; s < S; s += gridDim.x) {
+        const int *row = a + s * N;
+        for (long long w = tid; w < nw; w += 256) bm[w] = 0;
+        __syncthreads();
+        for (long long i = tid; i < N; i += 256) {
+            const int L = row[i];
+            atomicOr(&bm[L >> 5], 1u << (L & 31));
+        }
+        __syncthreads();
+        gt_scan(bm, pf, nw, part);
+        for (int j = 0; j < NT; j++) {
+            const int *cells = members + mstart[j];
+            const int n = msize[j];
+            for (long long w = tid; w < nw; w += 256) lb[w] = 0;
+            __syncthreads();
+            for (int q = tid; q < n; q += 256) {
+                const int L = row[cells[q]];
+                atomicOr(&lb[L >> 5], 1u << (L & 31));
+            }
+            __syncthreads();
+            const unsigned d = gt_scan(lb, lp, nw, part);
+            const long long base = hbase[j] + s * n;
+            for (int q = tid; q < n; q += 256) {
+                const int L = row[cells[q]];
+                const unsigned at = gt_rank(lb, lp, L);
+                atomicAdd(&hcnt[base + at], 1);
+                hrank[base + at] = (int)gt_rank(bm, pf, L);
+            }
+            if (tid == 0) hd[(size_t)j * S + s] = (int)d;
+            __syncthreads();
+        }
+    }
+}
+
+// one chunk of samples [s0, s0 + sc): P is its [sc][W][M] float32 trace.
+// Cluster k = blockIdx.y adds the rows rows[lo[k] .. hi[k]) (sample-major
+// global row indices s * W + rank, increasing s), or, never together
+// (ntj[k] >= 0), its histogram terms of every sample in the chunk.
+__global__ __launch_bounds__(256) void k_gt_accum(
+    const float *__restrict__ P, long long s0, int sc, long long S, int W,
+    long long M, const long long *__restrict__ rows,
+    const long long *__restrict__ lo, const long long *__restrict__ hi,
+    const int *__restrict__ ntj, const int *__restrict__ msize,
+    const long long *__restrict__ hbase, const int *__restrict__ hcnt,
+    const int *__restrict__ hrank, const int *__restrict__ hd,
+    double *__restrict__ acc)
+{
+    const int k = blockIdx.y;
+    const long long m = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (m >= M) return;
+    double v = acc[(size_t)k * M + m];
+    const long long base = s0 * W;
+    const int j = ntj[k];
+    if (j < 0) {
+        const long long e = hi[k];
+#pragma unroll 8
+        for (long long q = lo[k]; q < e; q++)
+            v += (double)P[(size_t)(rows[q] - base) * M + m];
+    } else {
+        const int n = msize[j];
+        for (int i = 0; i < sc; i++) {
+            const long long s = s0 + i;
+            const int *hc = hcnt + hbase[j] + s * n;
+            const int *hr = hrank + hbase[j] + s * n;
+            const int d = hd[(size_t)j * S + s];
+            double t = 0.0;
+            for (int q = 0; q < d; q++)
+                t += (double)hc[q] * (double)P[((size_t)i * W + hr[q]) * M + m];
+            v += t;
+        }
+    }
+    acc[(size_t)k * M + m] = v;
+}
+
+namespace {
+// device buffers of one bnpc_post_genotypes call, freed on every return
+struct GtBuffers {
+    void *p[32] = {};
+    int n = 0;
+    template <class T> hipError_t alloc(T **out, size_t count)
+    {
+        *out = nullptr;
+        hipError_t e = hipMalloc((void **)out, std::max<size_t>(count, 1) * sizeof(T));
+        if (e == hipSuccess) p[n++] = (void *)*out;
+        return e;
+    }
+    ~GtBuffers()
+    {
+        for (int i = 0; i < n; i++) (void)hipFree(p[i]);
+    }
+};
+
+// where a per-sample kernel's working set of `words` goes: LDS while it fits
+// (a workgroup per sample), else a global slice per workgroup
+struct GtArea {
+    unsigned grid = 0;
+    size_t lds = 0;
+    unsigned *scratch = nullptr;
+    long long stride = 0;
+};
+hipError_t gt_area(const void *kernel, long long words, int64_t S,
+                   GtBuffers &buf, GtArea &a)
+{
+    if ((size_t)words * 4 <= GT_LDS_MAX) {
+        a.grid = (unsigned)std::min<int64_t>(S, 65535);
+        a.lds = (size_t)words * 4;
+        return hipFuncSetAttribute(kernel,
+                                   hipFuncAttributeMaxDynamicSharedMemorySize,
+                                   (int)GT_LDS_MAX);
+    }
+    a.grid = (unsigned)std::min<int64_t>(S, GT_GLOBAL_WG);
+    a.stride = words;
+    return buf.alloc(&a.scratch, (size_t)a.grid * words);
+}
+}  // namespace
+
+extern "C" int bnpc_post_genotypes(bnpc_post *p, const int32_t *labels,
+                                   int64_t K, const float *params, int64_t W,
+                                   int64_t M, int64_t chunk, double *geno)
+{
+    if (!p || !labels || !params || !geno || K < 1 || K >= (int64_t)GT_MIXED
+        || W < 1 || M < 1 || chunk < 0) {
+        bnpc_set_error("bad argument: genotypes need labels, 1 <= K < 65534 "
+                       "clusters, a W >= 1 x M >= 1 trace and the output");
+        return 2;
+    }
+    if (!p->assign || !p->labels_in_range) {
+        bnpc_set_error("genotypes: the sample labels must lie in [0, N = %lld)",
+                       (long long)p->N);
+        return 2;
+    }
+    const int64_t S = p->S, N = p->N;
+    // the clusters: compact in [0, K), none empty; members grouped by cluster
+    std::vector<int64_t> start(K + 1, 0);
+    for (int64_t i = 0; i < N; i++) {
+        if (labels[i] < 0 || labels[i] >= K) {
+            bnpc_set_error("genotypes: cluster label %d of cell %lld is not in "
+                           "[0, %lld)", labels[i], (long long)i, (long long)K);
+            return 2;
+        }
+        start[labels[i] + 1]++;
+    }
+    for (int64_t k = 0; k < K; k++) {
+        if (start[k + 1] == 0) {
+            bnpc_set_error("genotypes: cluster %lld has no cells (labels must "
+                           "be compact)", (long long)k);
+            return 2;
+        }
+        start[k + 1] += start[k];
+    }
+    std::vector<int> members(N);
+    {
+        std::vector<int64_t> at(start.begin(), start.end() - 1);
+        for (int64_t i = 0; i < N; i++) members[at[labels[i]]++] = (int)i;
+    }
+    std::vector<unsigned short> cl(N);
+    for (int64_t i = 0; i < N; i++) cl[i] = (unsigned short)labels[i];
+
+    PCK(hipSetDevice(p->device));
+    GtBuffers buf;
+    unsigned short *d_cl;
+    unsigned char *d_flags;
+    int *d_rank, *d_distinct;
+    PCK(buf.alloc(&d_cl, N));
+    PCK(buf.alloc(&d_flags, (size_t)K * S));
+    PCK(buf.alloc(&d_rank, (size_t)K * S));
+    PCK(buf.alloc(&d_distinct, S));
+    PCK(hipMemcpy(d_cl, cl.data(), N * sizeof(unsigned short),
+                  hipMemcpyHostToDevice));
+
+    // pass 1
+    {
+        GtArea area;
+        PCK(gt_area((const void *)k_gt_flags, gt_flags_words(N, K), S, buf,
+                    area));
+        hipLaunchKernelGGL(k_gt_flags, dim3(area.grid), dim3(256), area.lds,
+                           0, p->assign, (long long)S, (long long)N, d_cl,
+                           (int)K, area.scratch, area.stride, d_flags, d_rank,
+                           d_distinct);
+        PCK(hipGetLastError());
+    }
+    std::vector<unsigned char> flags((size_t)K * S);
+    std::vector<int> rank((size_t)K * S), distinct(S);
+    PCK(hipMemcpy(flags.data(), d_flags, flags.size(), hipMemcpyDeviceToHost));
+    PCK(hipMemcpy(rank.data(), d_rank, rank.size() * sizeof(int),
+                  hipMemcpyDeviceToHost));
+    PCK(hipMemcpy(distinct.data(), d_distinct, S * sizeof(int),
+                  hipMemcpyDeviceToHost));
+
+    // the chosen samples of every cluster: together and alone, else
+    // together; a cluster never together goes to the histogram path
+    std::vector<long long> rows, lo0(K), hi0(K);
+    std::vector<double> den(K);
+    std::vector<int> ntj(K, -1), nt_cells;
+    std::vector<long long> nt_start, nt_base;
+    std::vector<int> nt_size;
+    long long hist_total = 0;
+    for (int64_t k = 0; k < K; k++) {
+        const unsigned char *f = flags.data() + (size_t)k * S;
+        bool any_alone = false, any_together = false;
+        for (int64_t s = 0; s < S; s++) {
+            any_together |= (f[s] & 1) != 0;
+            any_alone |= f[s] == 3;
+        }
+        lo0[k] = (long long)rows.size();
+        if (any_together) {
+            const unsigned char need = any_alone ? 3 : 1;
+            for (int64_t s = 0; s < S; s++) {
+                if ((f[s] & need) != need) continue;
+                const int r = rank[(size_t)k * S + s];
+                if (r >= W) {
+                    bnpc_set_error("genotypes: sample %lld needs row %d of a "
+                                   "trace %lld rows wide", (long long)s, r,
+                                   (long long)W);
+                    return 2;
+                }
+                rows.push_back((long long)s * W + r);
+            }
+            den[k] = (double)(rows.size() - lo0[k]);
+        } else {
+            const int64_t n = start[k + 1] - start[k];
+            for (int64_t s = 0; s < S; s++) {
+                if (distinct[s] > W) {
+                    bnpc_set_error("genotypes: sample %lld has %d clusters, "
+                                   "the trace %lld rows", (long long)s,
+                                   distinct[s], (long long)W);
+                    return 2;
+                }
+            }
+            ntj[k] = (int)nt_size.size();
+            nt_start.push_back(start[k]);
+            nt_size.push_back((int)n);
+            nt_base.push_back(hist_total);
+            hist_total += (long long)S * n;
+            den[k] = (double)(S * n);
+        }
+        hi0[k] = (long long)rows.size();
+    }
+    const int NT = (int)nt_size.size();
+
+    int *d_members = nullptr, *d_msize = nullptr, *d_hcnt = nullptr,
+        *d_hrank = nullptr, *d_hd = nullptr, *d_ntj;
+    long long *d_mstart = nullptr, *d_hbase = nullptr, *d_rows, *d_lo, *d_hi;
+    PCK(buf.alloc(&d_ntj, K));
+    PCK(hipMemcpy(d_ntj, ntj.data(), K * sizeof(int), hipMemcpyHostToDevice));
+    if (NT) {
+        // pass 1b
+        PCK(buf.alloc(&d_members, N));
+        PCK(buf.alloc(&d_mstart, NT));
+        PCK(buf.alloc(&d_msize, NT));
+        PCK(buf.alloc(&d_hbase, NT));
+        PCK(buf.alloc(&d_hcnt, hist_total));
+        PCK(buf.alloc(&d_hrank, hist_total));
+        PCK(buf.alloc(&d_hd, (size_t)NT * S));
+        PCK(hipMemcpy(d_members, members.data(), N * sizeof(int),
+                      hipMemcpyHostToDevice));
+        PCK(hipMemcpy(d_mstart, nt_start.data(), NT * sizeof(long long),
+                      hipMemcpyHostToDevice));
+        PCK(hipMemcpy(d_msize, nt_size.data(), NT * sizeof(int),
+                      hipMemcpyHostToDevice));
+        PCK(hipMemcpy(d_hbase, nt_base.data(), NT * sizeof(long long),
+                      hipMemcpyHostToDevice));
+        PCK(hipMemset(d_hcnt, 0, (size_t)hist_total * sizeof(int)));
+        GtArea area;
+        PCK(gt_area((const void *)k_gt_hist, gt_hist_words(N), S, buf, area));
+        hipLaunchKernelGGL(k_gt_hist, dim3(area.grid), dim3(256), area.lds, 0,
+                           p->assign, (long long)S, (long long)N, d_members,
+                           d_mstart, d_msize, d_hbase, NT, area.scratch,
+                           area.stride, d_hcnt, d_hrank, d_hd);
+        PCK(hipGetLastError());
+    }
+
+    // pass 2, the trace in chunks of samples
+    const size_t sample_floats = (size_t)W * M;
+    int64_t sc = chunk;
+    if (sc == 0)
+        sc = std::max<int64_t>(1, (int64_t)(((size_t)512 << 20)
+                                            / (sample_floats * sizeof(float))));
+    sc = std::min(sc, S);
+    float *d_P;
+    double *d_acc;
+    PCK(buf.alloc(&d_rows, rows.size()));
+    PCK(buf.alloc(&d_lo, K));
+    PCK(buf.alloc(&d_hi, K));
+    PCK(buf.alloc(&d_P, (size_t)sc * sample_floats));
+    PCK(buf.alloc(&d_acc, (size_t)K * M));
+    if (!rows.empty())
+        PCK(hipMemcpy(d_rows, rows.data(), rows.size() * sizeof(long long),
+                      hipMemcpyHostToDevice));
+    PCK(hipMemset(d_acc, 0, (size_t)K * M * sizeof(double)));
+    std::vector<long long> lo(K), hi(K), cursor(lo0);
+    for (int64_t s0 = 0; s0 < S; s0 += sc) {
+        const int64_t n = std::min(sc, S - s0);
+        const long long end = (long long)(s0 + n) * W;
+        for (int64_t k = 0; k < K; k++) {
+            lo[k] = cursor[k];
+            while (cursor[k] < hi0[k] && rows[cursor[k]] < end) cursor[k]++;
+            hi[k] = cursor[k];
+        }
+        PCK(hipMemcpy(d_lo, lo.data(), K * sizeof(long long),
+                      hipMemcpyHostToDevice));
+        PCK(hipMemcpy(d_hi, hi.data(), K * sizeof(long long),
+                      hipMemcpyHostToDevice));
+        PCK(hipMemcpy(d_P, params + (size_t)s0 * sample_floats,
+                      (size_t)n * sample_floats * sizeof(float),
+                      hipMemcpyHostToDevice));
+        hipLaunchKernelGGL(k_gt_accum,
+                           dim3((unsigned)((M + 255) / 256), (unsigned)K),
+                           dim3(256), 0, 0, d_P, (long long)s0, (int)n,
+                           (long long)S, (int)W, (long long)M, d_rows, d_lo,
+                           d_hi, d_ntj, d_msize, d_hbase, d_hcnt, d_hrank,
+                           d_hd, d_acc);
+        PCK(hipGetLastError());
+    }
+    PCK(hipMemcpy(geno, d_acc, (size_t)K * M * sizeof(double),
+                  hipMemcpyDeviceToHost));
+    for (int64_t k = 0; k < K; k++)
+        for (int64_t m = 0; m < M; m++) geno[(size_t)k * M + m] /= den[k];
     return 0;
 }

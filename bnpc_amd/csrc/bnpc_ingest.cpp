@@ -235,3 +235,56 @@ extern "C" int bnpc_unpack_codes(const uint64_t *planes, int64_t N, int64_t M,
     }
     return 0;
 }
+
+// Rows of a tab-separated table whose cells take one of K tokens per row
+// (the genotype tables of dpmmIO.save_geno: a row per mutation, a column per
+// cell, and a cell's entry is its cluster's value).  Token (r, j) is
+// blob[off[r * (K + 1) + j] .. off[r * (K + 1) + j + 1]); j = 0 is row r's
+// name, j = 1 + k cluster k's entry.  Row r is written as its name, then
+// for every cell c a tab and token (r, 1 + col[c]), then a newline; the rows
+// are appended to the file (the header line is the caller's).
+extern "C" int bnpc_write_table(const char *path, int64_t R, int64_t K,
+                                const char *blob, const int64_t *off,
+                                int64_t N, const int32_t *col)
+{
+    if (!path || R < 0 || K < 1 || N < 0 || (R && (!blob || !off))
+        || (N && !col)) {
+        bnpc_set_error("bad argument: write_table");
+        return 2;
+    }
+    for (int64_t c = 0; c < N; c++) {
+        if (col[c] < 0 || col[c] >= K) {
+            bnpc_set_error("write_table: column %lld takes token %d of %lld",
+                           (long long)c, col[c], (long long)K);
+            return 2;
+        }
+    }
+    FILE *f = fopen(path, "ab");
+    if (!f) {
+        bnpc_set_error("cannot open %s: %s", path, strerror(errno));
+        return 1;
+    }
+    std::vector<char> buf;
+    buf.reserve((size_t)8 << 20);
+    bool ok = true;
+    for (int64_t r = 0; r < R && ok; r++) {
+        const int64_t *o = off + r * (K + 1);
+        buf.insert(buf.end(), blob + o[0], blob + o[1]);
+        for (int64_t c = 0; c < N; c++) {
+            const int64_t j = 1 + col[c];
+            buf.push_back('\t');
+            buf.insert(buf.end(), blob + o[j], blob + o[j + 1]);
+        }
+        buf.push_back('\n');
+        if (buf.size() >= ((size_t)4 << 20) || r + 1 == R) {
+            ok = fwrite(buf.data(), 1, buf.size(), f) == buf.size();
+            buf.clear();
+        }
+    }
+    if (fclose(f) != 0) ok = false;
+    if (!ok) {
+        bnpc_set_error("write_table: short write on %s", path);
+        return 1;
+    }
+    return 0;
+}

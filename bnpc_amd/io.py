@@ -202,3 +202,70 @@ def get_out_dir(args, prefix=''):
             i += 1
     os.makedirs(out_dir, exist_ok=True)
     return out_dir
+
+
+# ---------------------------------------------------------------------------
+# genotype tables (dpmmIO.py:491-511)
+# ---------------------------------------------------------------------------
+def _write_rows(path, header, tokens, cols):
+    """The header line, then one row per row of `tokens` (rows x (1 + K)
+    strings: the row's name, then its K distinct entries), each cell c
+    taking entry cols[c] (libbnpc_hip.so's bnpc_write_table)."""
+    from bnpc_amd import _lib
+    with open(path, 'w') as f:
+        f.write('\t'.join([''] + [str(h) for h in header]) + '\n')
+    R, K1 = tokens.shape
+    enc = [t.encode() for t in tokens.ravel().tolist()]
+    off = np.zeros(len(enc) + 1, dtype=np.int64)
+    np.cumsum([len(e) for e in enc], out=off[1:])
+    blob = b''.join(enc)
+    col = np.ascontiguousarray(cols, dtype=np.int32)
+    _lib.check(_lib.load().bnpc_write_table(os.fsencode(path), R, K1 - 1,
+        blob, _lib.ptr(off), col.size, _lib.ptr(col)), 'write_table')
+
+
+def save_geno(out_dir, chain, est, values, cols, header, names=None):
+    """`save_geno` of the reference for one (chain, estimator) row: the
+    mutations x cells genotype table whose cell c is column cols[c] of
+    `values` (clusters x mutations, float64 for the posterior, the trace's
+    float32 for ML / MAP), under a header of the cells' cluster labels.
+    genotypes_<est>_<chain>.tsv holds the rounded 0/1 calls;
+    genotypes_cont_<est>_<chain>.tsv the values rounded to 4 decimals, if
+    any is not an integer.  Rows are named by `names` (the loader's mutation
+    names) when there is one per mutation, else 0..M-1.  Entries are
+    formatted as pandas' to_csv formats them (`astype(str)` of the dtype;
+    `round` is half-to-even, as DataFrame.round), once per distinct value."""
+    values = np.asarray(values)
+    M = values.shape[1]
+    index = np.arange(M)
+    if names is not None and np.asarray(names).size == M:
+        index = np.asarray(names)
+    index = np.array([str(x) for x in index.tolist()], dtype=object)
+    tag = f'{chain:0>2}'
+    rounded = np.round(values)
+
+    def table(entries):
+        return np.concatenate([index[:, None],
+            np.asarray(entries).T.astype(object)], axis=1)
+
+    paths = []
+    if not np.array_equal(rounded, values):
+        path = os.path.join(out_dir, f'genotypes_cont_{est}_{tag}.tsv')
+        _write_rows(path, header, table(np.round(values, 4).astype(str)),
+            cols)
+        paths.append(path)
+    path = os.path.join(out_dir, f'genotypes_{est}_{tag}.tsv')
+    _write_rows(path, header, table(rounded.astype(np.int64).astype(str)),
+        cols)
+    paths.append(path)
+    return paths
+
+
+def save_metric(path, column, rows):
+    """V_measure.txt / ARI.txt / hammingDist.txt (dpmmIO.py:514-542): a
+    tab-separated `chain  estimator  <column>` table, floats as to_csv
+    writes float64 (their repr)."""
+    with open(path, 'w') as f:
+        f.write(f'chain\testimator\t{column}\n')
+        for chain, est, score in rows:
+            f.write(f'{chain}\t{est}\t{float(score)!r}\n')

@@ -9,7 +9,10 @@ data-parallel kernel after the likelihood path (SURVEY.md section 8(f) rank
 4) - and the MPEAR score of every candidate cut run on the GPU (bnpc_post:
 the pair counts stay there, each candidate is one term of ONE pass over
 them); Ward's linkage and the tree cuts are SciPy on the host.
-Metrics (V-measure, ARI, Hamming) and tree helpers are out of scope.
+The per-cluster genotype averaging that follows is a device pass as well
+(bnpc_post_genotypes; host_genotypes is the host loop it is pinned to).
+The -tc / -td metrics (V-measure, ARI, Hamming; utils.py:49-72) are
+restated from integer counts at the end; tree helpers are out of scope.
 """
 import numpy as np
 
@@ -56,7 +59,8 @@ def point_estimate(result, est, data):
     clusters = np.unique(assignment)
     params = result['params'][k][np.arange(clusters.size)]
     row_of = {c: i for i, c in enumerate(clusters)}
-    geno = params[[row_of[c] for c in assignment]]          # cells x muts
+    cluster_of = np.array([row_of[c] for c in assignment], dtype=np.int64)
+    geno = params[cluster_of]                               # cells x muts
     called = geno.round()
     FN_geno = (((called == 1) & (data == 0)).sum() + EPSILON) \
         / (called.sum() + EPSILON)
@@ -64,6 +68,7 @@ def point_estimate(result, est, data):
         / ((1 - called).sum() + EPSILON)
     return {'step': step, 'a': result['DP_alpha'][step],
         'assignment': assignment.tolist(), 'genotypes': geno,
+        'cluster_genotypes': params, 'cluster_of': cluster_of,
         'FN': result['FN'][step], 'FP': result['FP'][step],
         'FN_geno': FN_geno, 'FP_geno': FP_geno}
 
@@ -202,17 +207,28 @@ def cut_tree_labels(tree, n_clusters):
 
 
 def get_MPEAR(assignments, dist=None):
-    """Ward tree on the mean distance, cut where MPEAR is largest
-    (utils.py:100-130).  Product path (dist is None): the pair counts are
+    """The MPEAR clustering (utils.py:100-130); see _mpear."""
+    assign, post = _mpear(assignments, dist)
+    if post is not None:
+        post.close()
+    return assign
+
+
+def _mpear(assignments, dist=None):
+    """(MPEAR clustering, the open Posterior or None): Ward tree on the mean
+    distance, cut where MPEAR is largest (utils.py:100-130).  Product path (dist is None): the pair counts are
     made and kept on the device, the mean distance comes to the host once
     for the linkage, and ALL candidate cuts are scored in one device pass
     over the counts (bnpc_post_mpear) - the float64 similarity `1 - dist`
     and the reference's pass over it per candidate are never made.  With a
-    given `dist` the scores are evaluated on the host (calc_MPEAR)."""
+    given `dist` the scores are evaluated on the host (calc_MPEAR).  The
+    product path hands its Posterior, samples still on the device, to the
+    caller, who closes it (mean_hierarchy_assignment: the genotype pass)."""
     from scipy.cluster.hierarchy import linkage
     from bnpc_amd import _lib
     assignments = np.asarray(assignments)
     post = None
+    done = False
     try:
         if dist is None:
             import os
@@ -243,7 +259,8 @@ def get_MPEAR(assignments, dist=None):
         if candidates.size == 0:
             # no candidate cut: the reference's loop does not run and its
             # best_assignment stays None (utils.py:116-130)
-            return None
+            done = True
+            return None, post
         # every candidate cut of the tree (cut_tree's labels, without its
         # O(N^2) replay of the merges: 12 s at 50 000 cells)
         cuts = cut_tree_labels(tree, candidates)
@@ -252,16 +269,18 @@ def get_MPEAR(assignments, dist=None):
             labels = np.ascontiguousarray(cuts.T)
             scores = mpear_scores(post.mpear_sums(labels), labels,
                 post.differ_sum, assignments.shape[0])
-            return _first_maximum(cuts, scores)
+            done = True
+            return _first_maximum(cuts, scores), post
         if dist is None:        # labels beyond uint16: the host scores
             dist = post.dist()
+        sim = 1 - dist
+        scores = np.array([calc_MPEAR(sim, np.ascontiguousarray(cuts[:, col]))
+            for col in range(candidates.size)])
+        done = True
+        return _first_maximum(cuts, scores), post
     finally:
-        if post is not None:
+        if post is not None and not done:
             post.close()
-    sim = 1 - dist
-    scores = np.array([calc_MPEAR(sim, np.ascontiguousarray(cuts[:, col]))
-        for col in range(candidates.size)])
-    return _first_maximum(cuts, scores)
 
 
 def _first_maximum(cuts, scores):
@@ -279,9 +298,38 @@ def _first_maximum(cuts, scores):
 def mean_hierarchy_assignment(assignments, params_full, dist=None):
     """utils.py:148-192: the MPEAR clustering and, per cluster, the mean of
     the sampled parameter vectors of the posterior samples in which the
-    cluster's cells sit together (and alone, if such samples exist)."""
+    cluster's cells sit together (and alone, if such samples exist).
+    Product path (dist is None): the Posterior of the MPEAR scoring, its
+    samples still on the device, runs the genotype pass too
+    (bnpc_post_genotypes, bit-identical to host_genotypes); with a given
+    `dist`, or cluster labels past uint16, the host loop."""
+    assign, params = _mean_hierarchy(assignments, params_full, dist)
+    return assign, params[assign].T
+
+
+def _mean_hierarchy(assignments, params_full, dist=None):
+    """(MPEAR clustering, per-cluster mean parameters (clusters, muts))"""
+    assign, post = _mpear(assignments, dist)
+    # the device pass runs on the samples the Posterior holds on the device;
+    # a clustering handle without it (a host stand-in for the pair counts)
+    # leaves the averaging to the host loop
+    device = getattr(post, 'genotypes', None)
+    try:
+        if device is not None and assign is not None \
+                and int(np.max(assign)) < 65534:
+            params = device(assign, params_full)
+        else:
+            params = host_genotypes(assignments, assign, params_full)
+    finally:
+        if post is not None:
+            post.close()
+    return assign, params
+
+
+def host_genotypes(assignments, assign, params_full):
+    """The per-cluster mean parameters of utils.py:148-192 on the host:
+    (clusters, muts) float64, row i for the i-th smallest label of assign."""
     steps = assignments.shape[0]
-    assign = get_MPEAR(assignments, dist)
     clusters = np.unique(assign)
     params = np.zeros((clusters.size, params_full.shape[2]))
     for row, cluster in enumerate(clusters):
@@ -309,7 +357,7 @@ def mean_hierarchy_assignment(assignments, params_full, dist=None):
                 rows = np.flatnonzero(np.isin(all_ids, ids))
                 params[row] += np.dot(cnt, params_full[s][rows])
             params[row] /= steps * cells.size
-    return assign, params[assign].T
+    return params
 
 
 def concat_chain_results(results):
@@ -328,8 +376,8 @@ def posterior_estimate(results, data):
     """`-e posterior` (the default estimator), chains pooled
     (utils.py:195-244)."""
     res = concat_chain_results(results)
-    assign, geno = mean_hierarchy_assignment(res['assignments'],
-        res['params'])
+    assign, params = _mean_hierarchy(res['assignments'], res['params'])
+    geno = params[assign].T
     called = geno.T.round()
     FN_geno = (((called == 1) & (data == 0)).sum() + EPSILON) \
         / (called.sum() + EPSILON)
@@ -337,6 +385,106 @@ def posterior_estimate(results, data):
         / ((1 - called).sum() + EPSILON)
     return {'a': (np.mean(res['DP_alpha']), np.std(res['DP_alpha'])),
         'assignment': assign.tolist(), 'genotypes': geno.T,
+        'cluster_genotypes': params, 'cluster_of': assign,
         'FN': (np.mean(res['FN']), np.std(res['FN'])),
         'FP': (np.mean(res['FP']), np.std(res['FP'])),
         'FN_geno': FN_geno, 'FP_geno': FP_geno}
+
+
+# ---------------------------------------------------------------------------
+# -tc / -td metrics (utils.py:49-72): scikit-learn's v_measure_score and
+# adjusted_rand_score restated from an integer contingency table (the
+# product does not import scikit-learn), the Hamming count of get_hamming_dist
+# ---------------------------------------------------------------------------
+def _contingency(labels_true, labels_pred):
+    """Non-zero cells of the contingency table (rows: true classes, columns:
+    inferred clusters) in column-major order - the order SciPy's sparse
+    `find` returns them in on the stack the golden files were written with
+    (its coo.sum_duplicates sorts by column first), which sets the
+    summation order of the mutual information; there the restatement is
+    bit-identical to scikit-learn, elsewhere within a few ulp.  Returns
+    (row, col, count), row sums, column sums."""
+    t = np.unique(np.asarray(labels_true), return_inverse=True)[1].ravel()
+    p = np.unique(np.asarray(labels_pred), return_inverse=True)[1].ravel()
+    if t.size != p.size:
+        raise ValueError('true and inferred clusterings differ in length: '
+            f'{t.size} != {p.size}')
+    height = int(t.max()) + 1 if t.size else 1
+    cells, count = np.unique(p.astype(np.int64) * height + t,
+        return_counts=True)
+    return cells % height, cells // height, count.astype(np.int64), \
+        np.bincount(t).astype(np.int64), np.bincount(p).astype(np.int64)
+
+
+def _entropy(counts):
+    """sklearn.metrics.cluster.entropy from the label counts"""
+    from math import log
+    pi = counts[counts > 0].astype(np.float64)
+    if pi.size <= 1:
+        return 0.0
+    pi_sum = np.sum(pi)
+    return -np.sum((pi / pi_sum) * (np.log(pi) - log(pi_sum)))
+
+
+def v_measure(labels_pred, labels_true):
+    """`v_measure_score(labels_true, labels_pred)` (utils.get_v_measure,
+    beta = 1): mutual information over the entropies of both clusterings."""
+    from math import log
+    if np.asarray(labels_true).size == 0:
+        return 1.0
+    row, col, nz, n_c, n_k = _contingency(labels_true, labels_pred)
+    h_c, h_k = _entropy(n_c), _entropy(n_k)
+    if n_c.size == 1 or n_k.size == 1:
+        mi = 0.0
+    else:
+        total = int(nz.sum())
+        log_nz = np.log(nz)
+        nz_frac = nz / total
+        outer = n_c.take(row) * n_k.take(col)
+        log_outer = -np.log(outer) + log(n_c.sum()) + log(n_k.sum())
+        terms = nz_frac * (log_nz - log(total)) + nz_frac * log_outer
+        terms = np.where(np.abs(terms) < np.finfo(terms.dtype).eps, 0.0,
+            terms)
+        mi = float(np.clip(terms.sum(), 0.0, None))
+    homogeneity = mi / h_c if h_c else 1.0
+    completeness = mi / h_k if h_k else 1.0
+    if homogeneity + completeness == 0.0:
+        return 0.0
+    return 2 * homogeneity * completeness / (homogeneity + completeness)
+
+
+def adjusted_rand(labels_pred, labels_true):
+    """`adjusted_rand_score(labels_true, labels_pred)` (utils.get_ARI) from
+    the pair confusion counts, in Python integers: at 50 000 cells the
+    products reach ~1e18."""
+    n = np.asarray(labels_true).size
+    row, col, nz, n_c, n_k = _contingency(labels_true, labels_pred)
+    nz = [int(x) for x in nz.tolist()]
+    sum_squares = sum(x * x for x in nz)
+    n_c, n_k = n_c.tolist(), n_k.tolist()
+    tp = sum_squares - n
+    fp = sum(x * n_k[j] for x, j in zip(nz, col.tolist())) - sum_squares
+    fn = sum(x * n_c[i] for x, i in zip(nz, row.tolist())) - sum_squares
+    tn = n * n - fp - fn - sum_squares
+    if fn == 0 and fp == 0:
+        return 1.0
+    return 2.0 * (tp * tn - fn * fp) / ((tp + fn) * (fn + tn)
+        + (tp + fp) * (fp + tn))
+
+
+def hamming_similarity(values, cols, true_data):
+    """`1 - get_hamming_dist(geno, true) / true.size` (dpmmIO.py:533-542,
+    utils.py:63-72): geno is the mutations x cells table whose cell c is
+    column cols[c] of `values` (clusters x mutations), rounded half-to-even;
+    true_data as loaded (cells x mutations by default).  Compared with the
+    truth transposed; if the shapes are equal, the smaller count of both
+    orientations; NaN in the truth is a mismatch."""
+    true_data = np.asarray(true_data)
+    called = np.round(np.asarray(values))[np.asarray(cols)]     # cells x muts
+    if true_data.shape != called.shape[::-1]:
+        score = np.count_nonzero(called != true_data)
+    else:
+        score = np.count_nonzero(called.T != true_data)
+        if called.shape == true_data.shape:
+            score = min(score, np.count_nonzero(called != true_data))
+    return 1 - score / true_data.size

@@ -953,6 +953,14 @@ int bnpc_gamma_logpdf_scalar(const bnpc_host_kernels *k, double x, double a,
 int bnpc_parse_matrix(const char *path, char sep, int skip_rows,
                       int skip_index, int8_t *out, int64_t *rows,
                       int64_t *cols);
+/* Appends R rows of a tab-separated table whose N cells per row take one of
+ * K tokens of that row (the genotype tables of dpmmIO.save_geno, written
+ * without formatting every entry): token (r, j) is blob[off[r * (K + 1) + j]
+ * .. off[r * (K + 1) + j + 1]), j = 0 the row's name, j = 1 + k the k-th
+ * entry; row r is its name, then per cell c a tab and token (r, 1 + col[c]),
+ * then a newline. */
+int bnpc_write_table(const char *path, int64_t R, int64_t K, const char *blob,
+                     const int64_t *off, int64_t N, const int32_t *col);
 
 /* ---- posterior co-clustering distance ------
  * differ[(i,j)] = number of the S posterior samples in which cells i < j carry
@@ -994,6 +1002,24 @@ int bnpc_post_ward(bnpc_post *post, double *Z_raw);
  * chain step whose row still knows its nearest neighbour needs no scan) */
 int bnpc_post_ward_stats(const bnpc_post *post, int64_t *scans,
                          int64_t *steps);
+/* Posterior genotypes (libs/utils.py:148-192, get_mean_hierarchy_assignment
+ * after _get_MPEAR): per cluster k of the MPEAR clustering, the mean of the
+ * sampled parameter rows `params_full[s][rank]` over the samples s in which
+ * k's cells share one label (and no other cell carries it, if such samples
+ * exist), rank being that label's position among the sample's distinct
+ * labels; a cluster never together takes, over all samples, `np.dot(counts,
+ * params_full[s][rows])` of the labels its cells carry, divided by S * n_k.
+ * Bit-exact to that loop: float64 sums of float32 rows in sample order (the
+ * dot terms in rank order from 0), the same divisions.
+ * The post's samples (bnpc_post_create, kept on the device) must lie in
+ * [0, N); labels: N int32, the cluster of every cell, compact in [0, K),
+ * K < 65534; params: the S x W x M float32 trace on the host, streamed to
+ * the device `chunk` samples at a time (0: about 512 MB per chunk); geno:
+ * K x M float64.  Return code 2, and nothing launched, for labels out of
+ * range or a sample whose chosen row lies past W. */
+int bnpc_post_genotypes(bnpc_post *post, const int32_t *labels, int64_t K,
+                        const float *params, int64_t W, int64_t M,
+                        int64_t chunk, double *geno);
 int bnpc_post_destroy(bnpc_post *post);
 
 #ifdef __cplusplus

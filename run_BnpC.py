@@ -7,10 +7,13 @@ libs/CRP_learning_errors.py of this repo).
 
 Kept verbatim from the reference: every flag, its destination name, type,
 default and choices - including the defaults that differ from their help text
-(-FP_m 0.01, -sms 3) and `-t` being store_false.  Outputs are restated
-minimally (file I/O and reporting are out of scope):
-args.txt, assignment.txt and errors.txt for the posterior (MPEAR, chains
-pooled), ML and MAP estimators; plots, genotype tables and metrics are not
+(-FP_m 0.01, -sms 3) and `-t` being store_false.  Outputs (dpmmIO.py
+save_run, save_geno, save_v_measure, save_ARI, save_hamming_dist): args.txt,
+assignment.txt and errors.txt for the posterior (MPEAR, chains pooled), ML
+and MAP estimators; per estimator the inferred genotypes
+(genotypes_<est>_<chain>.tsv, and genotypes_cont_<est>_<chain>.tsv when they
+are not all 0/1); with -tc V_measure.txt and ARI.txt, with -td
+hammingDist.txt.  Plots, the similarity PDF and -tr tree colouring are not
 part of this build.
 """
 import argparse
@@ -105,9 +108,10 @@ FLAGS = [
     ('output', '-tr', '--tree', dict(type=str, default='',
         help='Accepted for compatibility (tree colouring is out of scope).')),
     ('output', '-tc', '--true_clusters', dict(type=str, default='',
-        help='Accepted for compatibility (metrics are out of scope).')),
+        help='File with the true cluster assignment: writes V_measure.txt '
+        'and ARI.txt.')),
     ('output', '-td', '--true_data', dict(type=str, default='',
-        help='Accepted for compatibility (metrics are out of scope).')),
+        help='File with the true (error-free) data: writes hammingDist.txt.')),
 ]
 
 
@@ -132,12 +136,15 @@ def parse_args(argv=None):
     return build_parser().parse_args(argv)
 
 
-def save_outputs(args, results, data, out_dir):
+def save_outputs(args, results, data, out_dir, names=None):
+    """The output files of one run; names: the loader's (cell, mutation)
+    names, which name the genotype tables' rows."""
+    from bnpc_amd import io as bio
     from bnpc_amd import postproc
     ests = [args.estimator] if isinstance(args.estimator, str) \
         else list(args.estimator)
     chains = list(enumerate(results)) if args.single_chains else [('mean', None)]
-    rows_a, rows_e = [], []
+    rows_a, rows_e, inferred = [], [], []
     for est in ests:
         if est == 'posterior':
             # the reference's per-chain posterior (-sc) indexes its parameter
@@ -145,6 +152,7 @@ def save_outputs(args, results, data, out_dir):
             inf = postproc.posterior_estimate(results, data)
             rows_a.append(('mean', est,
                 ' '.join(str(i) for i in inf['assignment'])))
+            inferred.append(('mean', est, inf))
             rows_e.append(('mean', est,
                 f'{inf["FN"][0]:.4f}+-{inf["FN"][1]:.4f}',
                 round(float(inf['FN_geno']), 4),
@@ -159,6 +167,7 @@ def save_outputs(args, results, data, out_dir):
             inf = postproc.point_estimate(res, est, data)
             rows_a.append((chain, est,
                 ' '.join(str(i) for i in inf['assignment'])))
+            inferred.append((chain, est, inf))
             rows_e.append((chain, est, round(float(inf['FN']), 4),
                 round(float(inf['FN_geno']), 4), round(float(inf['FP']), 8),
                 round(float(inf['FP_geno']), 8)))
@@ -179,6 +188,28 @@ def save_outputs(args, results, data, out_dir):
             if key == 'time':
                 val = [f'{t:%Y%m%d_%H:%M:%S}' for t in val]
             f.write(f'{key}: {val}\n')
+    mut_names = names[1] if names is not None else None
+    for chain, est, inf in inferred:
+        bio.save_geno(out_dir, chain, est, inf['cluster_genotypes'],
+            inf['cluster_of'], inf['assignment'], mut_names)
+    # the metric tables list their rows chain by chain, as the reference
+    # does (its per-chain dictionary, dpmmIO.py:524-530); the pooled
+    # posterior first
+    inferred.sort(key=lambda row: -1 if row[0] == 'mean' else row[0])
+    if args.true_clusters:
+        true_assign = bio.load_txt(args.true_clusters)
+        bio.save_metric(os.path.join(out_dir, 'V_measure.txt'), 'V-measure',
+            [(c, e, postproc.v_measure(inf['assignment'], true_assign))
+                for c, e, inf in inferred])
+        bio.save_metric(os.path.join(out_dir, 'ARI.txt'), 'ARI',
+            [(c, e, postproc.adjusted_rand(inf['assignment'], true_assign))
+                for c, e, inf in inferred])
+    if args.true_data:
+        true_data = bio.load_data(args.true_data, transpose=args.transpose)
+        bio.save_metric(os.path.join(out_dir, 'hammingDist.txt'),
+            '1 - norm Hamming distance',
+            [(c, e, postproc.hamming_similarity(inf['cluster_genotypes'],
+                inf['cluster_of'], true_data)) for c, e, inf in inferred])
 
 
 def main(args):
@@ -193,8 +224,9 @@ def main(args):
         # device take them as they are (no float64 matrix)
         from bnpc_amd import bitplanes
         data = bitplanes.load_matrix(args.input, transpose=args.transpose)
+        names = None
     else:
-        data, _ = bio.load_data(args.input, transpose=args.transpose,
+        data, names = bio.load_data(args.input, transpose=args.transpose,
             get_names=True)
     assert data.size > 0, f'Could not read data from file: {args.input}'
 
@@ -240,7 +272,7 @@ def main(args):
         print(f'\nWriting output to: {out_dir}\n')
     if hasattr(data, 'planes'):
         data = data.codes()     # 0 | 1 | 3: all the estimators compare with
-    save_outputs(args, results, data, out_dir)
+    save_outputs(args, results, data, out_dir, names)
     return results
 
 

@@ -1,7 +1,15 @@
 #!/usr/bin/env python3
 """Phases of the posterior estimator's clustering step (postproc.get_MPEAR) on
 synthetic posterior samples: N cells, S samples around C true clusters.
-usage: posterior_bench.py N S [C]"""
+usage: posterior_bench.py N S [C]
+
+With GENO_M=<mutations> the genotype pass follows on the best cut, with a
+random float32 trace of GENO_W (default C + 8) rows per sample: the device
+pass (bnpc_post_genotypes, trace upload included; its kernels alone:
+rocprofv3 --kernel-trace --stats) and - GENO_HOST=1 - the host loop
+(postproc.host_genotypes).
+GENO_TABLE=<dir>: the genotype table writer (io.save_geno) into that
+directory, files removed afterwards."""
 import os
 import sys
 import time
@@ -58,6 +66,34 @@ best = int(np.argmax(scores))
 t0 = lap('scores from the integers (host)', t0)
 print(f'  total {time.perf_counter() - t_all:.3f} s; best cut: '
     f'{cand[best]} clusters, MPEAR {scores[best]:.6f}')
+GENO_M = int(os.environ.get('GENO_M', '0'))
+if GENO_M:
+    W = int(os.environ.get('GENO_W', str(C + 8)))
+    assign = np.ascontiguousarray(cuts[:, best])
+    params = np.empty((S, W, GENO_M), dtype=np.float32)
+    for s in range(S):
+        params[s] = rng.random_sample((W, GENO_M))
+    print(f'genotypes: K={cand[best]} M={GENO_M} W={W}, trace '
+        f'{params.nbytes / 1e9:.2f} GB')
+    t0 = time.perf_counter()
+    geno = post.genotypes(assign, params)
+    t0 = lap('device pass (bnpc_post_genotypes, upload included)', t0)
+    if os.environ.get('GENO_HOST') == '1':
+        want = postproc.host_genotypes(a, assign, params)
+        t0 = lap('host loop (postproc.host_genotypes)', t0)
+        print('  device == host:', np.array_equal(geno, want))
+    out_dir = os.environ.get('GENO_TABLE')
+    if out_dir:
+        from bnpc_amd import io as bio
+        os.makedirs(out_dir, exist_ok=True)
+        t0 = time.perf_counter()
+        paths = bio.save_geno(out_dir, 'mean', 'posterior', geno, assign,
+            assign.tolist())
+        t0 = lap('genotype tables written (io.save_geno)', t0)
+        for path in paths:
+            print(f'    {os.path.basename(path)}: '
+                f'{os.path.getsize(path) / 1e9:.2f} GB')
+            os.remove(path)
 post.close()
 if len(sys.argv) > 4:       # the reference-order host evaluation, one candidate
     d = _lib.codist(a) / S
