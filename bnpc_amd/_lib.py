@@ -5,6 +5,7 @@ HIP call fails, a RuntimeError is raised.
 """
 import ctypes as C
 import os
+import re
 
 import numpy as np
 
@@ -500,9 +501,15 @@ def host_settings(n_chains, n_devices, nodes=None, apply=True,
         os.environ['BNPC_HOST_SHARE'] = str(share)
         if not greedy:
             os.environ.setdefault('BNPC_HOST_SPIN_US', '5')
-    out['spin_us'] = int(os.environ.get('BNPC_HOST_SPIN_US') or 300) \
-        if apply else (300 if greedy else 5)
+    out['spin_us'] = host_spin_us() if apply else (300 if greedy else 5)
     return out
+
+
+def host_spin_us():
+    """BNPC_HOST_SPIN_US as the library reads it (bnpc_host_spin_ns): the
+    value's leading integer, 300 when it is unset or has none."""
+    m = re.match(r'\s*[+-]?\d+', os.environ.get('BNPC_HOST_SPIN_US', ''))
+    return int(m.group()) if m else 300
 
 
 _affinity = {'pid': None, 'original': None, 'bound': 0}

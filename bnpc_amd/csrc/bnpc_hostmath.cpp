@@ -20,16 +20,13 @@
 // for two real terms.
 
 #include <limits.h>
-#include <linux/futex.h>
 #include <math.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 #include <pthread.h>
-#include <sys/syscall.h>
 #include <time.h>
-#include <unistd.h>
 
 #include <algorithm>
 #include <atomic>
@@ -61,20 +58,15 @@ namespace {
 // itself) - none does.
 class Team {
 public:
-    Team() : pid_(getpid())
-    {
-        // (300 us: the ranks a converged step uses stay awake from one of its
-        // batches to the next; a chain that shares its NUMA node with others
-        // is given 5 by its driver - bnpc_amd.mcmc, bench.py)
-        const char *e = getenv("BNPC_HOST_SPIN_US");
-        spin_ns_ = (e ? atol(e) : 300) * 1000L;
-    }
+    // (300 us: the ranks a converged step uses stay awake from one of its
+    // batches to the next; a chain that shares its NUMA node with others is
+    // given 5 by its driver - bnpc_amd.mcmc, bench.py)
+    Team() : spin_ns_(bnpc_host_spin_ns()) {}
     // a chain whose driver gave it the short spin (it has fewer than a
     // handful of CPUs to itself) is frugal with ranks as well: every rank it
     // wakes is taken from a neighbour
     bool frugal() const { return spin_ns_ < 50000; }
     int size() const { return ranks_.load(std::memory_order_acquire); }
-    pid_t pid() const { return pid_; }
 
     // Workers up to `ranks` ranks in all (the caller is rank 0).  The team
     // grows IN PLACE: a late starter begins with seen = 0 and takes the word
@@ -117,37 +109,20 @@ public:
         // up (the generation in the upper half keeps a late worker of the
         // previous job from drawing a rank of this one)
         ticket_.store(((uint64_t)gen_ << 32) | 1u, std::memory_order_relaxed);
-        // store the word, THEN look for sleepers - in that order for every
-        // observer (a full fence: x86 may otherwise satisfy the load before
-        // the store is visible, while a worker that has just announced itself
-        // still reads the old word in futex_wait, and nobody wakes it)
         word_.store((gen_ << 8) | (uint32_t)n, std::memory_order_seq_cst);
-        std::atomic_thread_fence(std::memory_order_seq_cst);
         // as many sleepers as ranks are wanted, not the whole team: any worker
         // can take any rank, and a 32-thread team that is woken for a 3-rank
         // job costs 29 pointless context switches
-        if (sleepers_.load(std::memory_order_seq_cst) > 0)
-            syscall(SYS_futex, (uint32_t *)&word_, FUTEX_WAKE_PRIVATE, n - 1,
-                    nullptr, nullptr, 0);
+        bnpc_unpark(word_, n - 1, sleepers_);
         fn(0);
-        while (pending_.load(std::memory_order_acquire) != 0) cpu_relax();
+        bnpc_spin_until([this] {
+            return pending_.load(std::memory_order_acquire) == 0;
+        });
         job_.store(nullptr, std::memory_order_relaxed);
         return n;
     }
 
 private:
-    static void cpu_relax()
-    {
-#if defined(__x86_64__)
-        __builtin_ia32_pause();
-#endif
-    }
-    static long now_ns()
-    {
-        timespec ts;
-        clock_gettime(CLOCK_MONOTONIC, &ts);
-        return ts.tv_sec * 1000000000L + ts.tv_nsec;
-    }
     void loop(int /* creation order: ranks are drawn per job */)
     {
         uint32_t seen = 0;      // the word before the first job (a worker
@@ -161,22 +136,9 @@ private:
                                 // dozen more of a wide batch would burn a
                                 // core each until the next one
         for (;;) {
-            uint32_t w;
-            const long t0 = now_ns();
             const long spin = !worked ? 0
                 : (last_slot < 8 || spin_ns_ < 50000 ? spin_ns_ : 50000);
-            int polls = 0;
-            while ((w = word_.load(std::memory_order_acquire)) == seen) {
-                cpu_relax();
-                if ((++polls & 63) == 0 && now_ns() - t0 > spin) {
-                    sleepers_.fetch_add(1, std::memory_order_seq_cst);
-                    // re-checked by the kernel: returns at once if the word
-                    // has moved on
-                    syscall(SYS_futex, (uint32_t *)&word_, FUTEX_WAIT_PRIVATE,
-                            seen, nullptr, nullptr, 0);
-                    sleepers_.fetch_sub(1, std::memory_order_acq_rel);
-                }
-            }
+            const uint32_t w = bnpc_park(word_, seen, spin, sleepers_);
             seen = w;
             // draw a rank of THIS job (generation w >> 8), if one is left
             const int n = (int)(w & 0xff);
@@ -200,8 +162,7 @@ private:
         }
     }
 
-    pid_t pid_;
-    long spin_ns_ = 50000;
+    long spin_ns_;
     std::mutex job_mu_;
     std::vector<std::thread> threads_;
     std::atomic<int> ranks_{1};         // the caller + threads_.size()
@@ -212,36 +173,6 @@ private:
     std::atomic<const std::function<void(int)> *> job_{nullptr};
 };
 
-// The team of this PROCESS.  A forked child inherits the object but not the
-// threads: it abandons the parent's team (never destroyed - its std::threads
-// are not joinable there, and its job lock may be held by a thread that does
-// not exist in the child) and starts its own on first use.
-Team *g_team = nullptr;
-std::mutex g_team_mu;
-
-void team_after_fork_child()
-{
-    // the registry lock may have been held by another thread of the parent
-    new (&g_team_mu) std::mutex();
-    g_team = nullptr;
-}
-
-Team *team_for(int threads)
-{
-    static const int hooked = pthread_atfork(nullptr, nullptr,
-                                             team_after_fork_child);
-    (void)hooked;
-    Team *t;
-    {
-        std::lock_guard<std::mutex> lk(g_team_mu);
-        if (g_team && g_team->pid() != getpid()) g_team = nullptr;
-        if (!g_team) g_team = new Team();
-        t = g_team;
-    }
-    if (t->size() < threads) t->grow(threads);
-    return t;
-}
-
 // ---------------------------------------------------------------------------
 // the aside: ONE more persistent thread per process, for a job that runs NEXT
 // TO the calling thread instead of with it (bnpc_aside_start / _wait,
@@ -249,20 +180,23 @@ Team *team_for(int threads)
 // copy of the stream while the caller waits for the sweep's kernel and walks
 // its loop.  Parks on a futex word after the team's spin; rebuilt after
 // fork() like the team.
+//
+// Threading contract (include/bnpc_hip.h): one job at a time.  start() holds
+// the aside's post lock while it waits for the job before and posts its own,
+// so posters on several host threads take turns and no posted job is
+// overwritten; wait() returns when the aside is idle (after a later poster's
+// job too, if one came).  An aside job must not post to the aside (it would
+// wait for itself) or start a team job (its poster may hold the team) - the
+// walker does neither.
 // ---------------------------------------------------------------------------
 class Aside {
 public:
-    Aside() : pid_(getpid())
-    {
-        const char *e = getenv("BNPC_HOST_SPIN_US");
-        spin_ns_ = (e ? atol(e) : 300) * 1000L;
-    }
-    pid_t pid() const { return pid_; }
+    Aside() : spin_ns_(bnpc_host_spin_ns()) {}
 
-    // post fn (copied); false: no thread to be had - nothing was posted.
-    // One job at a time: the caller has waited for the previous one.
+    // post fn (copied); false: no thread to be had - nothing was posted
     bool start(const std::function<void()> &fn)
     {
+        std::lock_guard<std::mutex> hold(post_mu_);
         wait();
         if (!started_) {
             try {
@@ -275,60 +209,29 @@ public:
         job_ = fn;
         running_.store(1, std::memory_order_release);
         word_.fetch_add(1, std::memory_order_seq_cst);
-        std::atomic_thread_fence(std::memory_order_seq_cst);
-        if (sleeping_.load(std::memory_order_seq_cst) > 0)
-            syscall(SYS_futex, (uint32_t *)&word_, FUTEX_WAKE_PRIVATE, 1,
-                    nullptr, nullptr, 0);
+        bnpc_unpark(word_, 1, sleeping_);
         return true;
     }
 
     void wait()
     {
-        for (int spins = 0; running_.load(std::memory_order_acquire);
-             spins++) {
-            if (spins < 2048) {
-#if defined(__x86_64__)
-                __builtin_ia32_pause();
-#endif
-            } else {
-                std::this_thread::yield();
-            }
-        }
+        bnpc_spin_until([this] {
+            return running_.load(std::memory_order_acquire) == 0;
+        }, 2048);
     }
 
 private:
-    static long now_ns()
-    {
-        timespec ts;
-        clock_gettime(CLOCK_MONOTONIC, &ts);
-        return ts.tv_sec * 1000000000L + ts.tv_nsec;
-    }
     void loop()
     {
-        uint32_t seen = 0;
-        for (;;) {
-            uint32_t w;
-            const long t0 = now_ns();
-            int polls = 0;
-            while ((w = word_.load(std::memory_order_acquire)) == seen) {
-#if defined(__x86_64__)
-                __builtin_ia32_pause();
-#endif
-                if ((++polls & 63) == 0 && now_ns() - t0 > spin_ns_) {
-                    sleeping_.fetch_add(1, std::memory_order_seq_cst);
-                    syscall(SYS_futex, (uint32_t *)&word_, FUTEX_WAIT_PRIVATE,
-                            seen, nullptr, nullptr, 0);
-                    sleeping_.fetch_sub(1, std::memory_order_acq_rel);
-                }
-            }
-            seen = w;
+        for (uint32_t seen = 0;;) {
+            seen = bnpc_park(word_, seen, spin_ns_, sleeping_);
             job_();
             running_.store(0, std::memory_order_release);
         }
     }
 
-    pid_t pid_;
-    long spin_ns_ = 300000;
+    long spin_ns_;
+    std::mutex post_mu_;
     bool started_ = false;
     std::thread thread_;
     std::function<void()> job_;
@@ -336,14 +239,47 @@ private:
     std::atomic<int> running_{0}, sleeping_{0};
 };
 
+// The team and the aside of this PROCESS, created under one registry lock.  A
+// forked child inherits the objects but not the threads: it abandons the
+// parent's (never destroyed - their std::threads are not joinable there, and
+// their locks may be held by a thread that does not exist in the child) and
+// starts its own on first use.
+Team *g_team = nullptr;
 Aside *g_aside = nullptr;
+std::mutex g_registry_mu;
 
-// (the calling thread of a chain only: no lock - and a forked child starts
-// its own, the parent's object is abandoned like its team)
-Aside *aside()
+void after_fork_child()
 {
-    if (g_aside && g_aside->pid() != getpid()) g_aside = nullptr;
-    if (!g_aside) g_aside = new Aside();
+    // the registry lock may have been held by another thread of the parent
+    new (&g_registry_mu) std::mutex();
+    g_team = nullptr;
+    g_aside = nullptr;
+}
+
+std::mutex &registry()
+{
+    static const int hooked = pthread_atfork(nullptr, nullptr,
+                                             after_fork_child);
+    (void)hooked;
+    return g_registry_mu;
+}
+
+Team *team_for(int threads)
+{
+    Team *t;
+    {
+        std::lock_guard<std::mutex> lk(registry());
+        if (!g_team) g_team = new Team();
+        t = g_team;
+    }
+    if (t->size() < threads) t->grow(threads);
+    return t;
+}
+
+Aside *aside(bool create)
+{
+    std::lock_guard<std::mutex> lk(registry());
+    if (!g_aside && create) g_aside = new Aside();
     return g_aside;
 }
 
@@ -351,12 +287,12 @@ Aside *aside()
 
 bool bnpc_aside_start(const std::function<void()> &fn)
 {
-    return aside()->start(fn);
+    return aside(true)->start(fn);
 }
 
 void bnpc_aside_wait()
 {
-    if (g_aside && g_aside->pid() == getpid()) g_aside->wait();
+    if (Aside *a = aside(false)) a->wait();
 }
 
 // ranks a team of `threads` will really have: the team is capped at 255 and
@@ -888,17 +824,11 @@ extern "C" int bnpc_mh_batch(const bnpc_host_kernels *k, bnpc_mt19937 *rng,
         auto add_rows_up = [&]() {
             // (uniform prior: prior_out holds zeros - the sum of zeros)
             for (int64_t g = seq_next; g < G; g++) {
-                for (long spins = 0; row_left[(size_t)g].load(
-                         std::memory_order_acquire) != 0; spins++) {
-                    if (bail.load(std::memory_order_relaxed)) return;
-                    if (spins < 2000) {
-#if defined(__x86_64__)
-                        __builtin_ia32_pause();
-#endif
-                    } else {
-                        std::this_thread::yield();
-                    }
-                }
+                bnpc_spin_until([&] {
+                    return row_left[(size_t)g].load(std::memory_order_acquire)
+                        == 0 || bail.load(std::memory_order_relaxed);
+                }, 2000);
+                if (bail.load(std::memory_order_relaxed)) return;
                 const double *d = a->prior_out + (size_t)g * M;
                 int64_t m = 0;
                 if (!seq_started) {
@@ -1129,16 +1059,9 @@ extern "C" int bnpc_mh_batch(const bnpc_host_kernels *k, bnpc_mt19937 *rng,
             // the draws of this cluster are a few microseconds away at most
             // (a short spin; beyond it the waiters get out of the way of the
             // thread that draws - they may share its core)
-            for (int spins = 0;
-                 rows_ready.load(std::memory_order_acquire) <= g; spins++) {
-                if (spins < 256) {
-#if defined(__x86_64__)
-                    __builtin_ia32_pause();
-#endif
-                } else {
-                    std::this_thread::yield();
-                }
-            }
+            bnpc_spin_until([&] {
+                return rows_ready.load(std::memory_order_acquire) > g;
+            }, 256);
             if (bail.load(std::memory_order_relaxed)) continue;
             const int64_t m0 = ch * blk;
             const int64_t m1 = m0 + blk < M ? m0 + blk : M;

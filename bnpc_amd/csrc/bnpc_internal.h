@@ -10,7 +10,93 @@
 void bnpc_set_error(const char *fmt, ...);
 
 #ifdef __cplusplus
+#include <linux/futex.h>
+#include <stdlib.h>
+#include <sys/syscall.h>
+#include <time.h>
+#include <unistd.h>
+
+#include <atomic>
 #include <functional>
+#include <thread>
+
+// ---- waiting on the host threads (the caller, the team, the aside) ---------
+// the spin-wait hint
+static inline void bnpc_cpu_relax()
+{
+#if defined(__x86_64__)
+    __builtin_ia32_pause();
+#endif
+}
+
+static inline long bnpc_now_ns()
+{
+    timespec ts;
+    clock_gettime(CLOCK_MONOTONIC, &ts);
+    return ts.tv_sec * 1000000000L + ts.tv_nsec;
+}
+
+// Poll ready() until it holds: a pause between the first `pauses` polls, then
+// the core is yielded between polls (a waiter may share its core with the
+// thread it waits for).  A wait that can be given up folds its flag into
+// ready() and checks the flag again afterwards.
+template <class Ready>
+static inline void bnpc_spin_until(Ready ready, long pauses = 2048)
+{
+    for (long spins = 0; !ready(); spins++) {
+        if (spins < pauses) bnpc_cpu_relax();
+        else std::this_thread::yield();
+    }
+}
+
+// A persistent thread waits for `word` to move on from `seen`: it polls for
+// spin_ns, then sleeps in FUTEX_WAIT, counted in `sleepers` while it does.
+// Returns the new word.  The poster stores the word, then calls bnpc_unpark.
+static inline uint32_t bnpc_park(std::atomic<uint32_t> &word, uint32_t seen,
+                                 long spin_ns, std::atomic<int> &sleepers)
+{
+    const long t0 = bnpc_now_ns();
+    int polls = 0;
+    uint32_t w;
+    while ((w = word.load(std::memory_order_acquire)) == seen) {
+        bnpc_cpu_relax();
+        if ((++polls & 63) == 0 && bnpc_now_ns() - t0 > spin_ns) {
+            sleepers.fetch_add(1, std::memory_order_seq_cst);
+            // re-checked by the kernel: returns at once if the word has
+            // moved on
+            syscall(SYS_futex, (uint32_t *)&word, FUTEX_WAIT_PRIVATE, seen,
+                    nullptr, nullptr, 0);
+            sleepers.fetch_sub(1, std::memory_order_acq_rel);
+        }
+    }
+    return w;
+}
+
+// Wake up to n sleepers after a (seq_cst) store to the word: the word, THEN
+// the sleepers - in that order for every observer (a full fence: x86 may
+// otherwise satisfy the load before the store is visible, while a thread that
+// has just announced itself still reads the old word in FUTEX_WAIT, and
+// nobody wakes it).
+static inline void bnpc_unpark(std::atomic<uint32_t> &word, int n,
+                               std::atomic<int> &sleepers)
+{
+    std::atomic_thread_fence(std::memory_order_seq_cst);
+    if (sleepers.load(std::memory_order_seq_cst) > 0)
+        syscall(SYS_futex, (uint32_t *)&word, FUTEX_WAKE_PRIVATE, n, nullptr,
+                nullptr, 0);
+}
+
+// BNPC_HOST_SPIN_US in nanoseconds: how long a parked thread polls before it
+// sleeps.  The value's leading integer; 300 us when it is unset or has none
+// (bnpc_amd._lib.host_settings reads it the same way).
+static inline long bnpc_host_spin_ns()
+{
+    const char *e = getenv("BNPC_HOST_SPIN_US");
+    char *end = nullptr;
+    const long us = e ? strtol(e, &end, 10) : 0;
+    return (e && end != e ? us : 300) * 1000L;
+}
+
 // fn(rank) for every rank 0..n-1, n = bnpc_team_ranks(threads), on this
 // process's host thread team (the caller is rank 0; the team grows to n if it
 // is smaller - bnpc_team_ranks does that and returns fewer when the system
@@ -20,8 +106,10 @@ int bnpc_team_ranks(int threads);
 int bnpc_team_run(int threads, const std::function<void(int)> &fn);
 // fn() on the process's one aside thread, NEXT TO the caller (it returns at
 // once; false: no thread to be had, nothing runs); bnpc_aside_wait returns
-// when that job is over.  One job at a time, posted and awaited by the thread
-// that drives the chain.
+// when that job is over.  One job at a time: a poster waits for the job
+// before it, so concurrent posters take turns (bnpc_aside_wait may then also
+// wait for another thread's job).  An aside job must not post to the aside or
+// start a team job.
 bool bnpc_aside_start(const std::function<void()> &fn);
 void bnpc_aside_wait();
 #endif

@@ -576,9 +576,7 @@ static int wait_done(bnpc_ctx *c, int slot, unsigned seq)
                 std::atomic_thread_fence(std::memory_order_acquire);
                 return 0;
             }
-#if defined(__x86_64__)
-            __builtin_ia32_pause();
-#endif
+            bnpc_cpu_relax();
         }
     }
     HIPCHK(hipStreamSynchronize(c->stream));
@@ -3901,19 +3899,24 @@ static void mh_ahead_drop(bnpc_ctx *c)
     ah->active = false;
 }
 
-// A small batch (the rows of a restricted scan) takes a walker's rows whole:
-// the number adopted (the live stream then stands behind them), 0 if there is
-// no walker or the live stream stands elsewhere.
-static int64_t mh_ahead_adopt(bnpc_ctx *c, bnpc_mt19937 *rng, int64_t G,
-                              int64_t M, int64_t n_sd)
+// A batch of G rows claims a walker's rows: they are kept iff the batch fits
+// them (`fits`: the caller's conditions, then stream, M and n_sd) and the live
+// stream stands exactly where the walker's stood when it began to draw.
+// Returns the number adopted (counted on the context); 0: the walker is
+// dropped.
+static int64_t mh_ahead_claim(bnpc_ctx *c, bool fits, const bnpc_mt19937 *rng,
+                              int64_t G, int64_t M, int64_t n_sd)
 {
     MhAhead *ah = c->ahead;
     if (!ah || !ah->active) return 0;
-    bool ok = rng && ah->M == M && ah->n_sd == n_sd && c->tun.mh_ahead != 3;
+    bool ok = fits && rng && ah->M == M && ah->n_sd == n_sd
+        && c->tun.mh_ahead != 3;
     if (ok) {
-        int known;
-        while ((known = ah->start_known.load(std::memory_order_acquire)) == 0)
-            __builtin_ia32_pause();
+        int known = 0;
+        bnpc_spin_until([&] {
+            return (known = ah->start_known.load(std::memory_order_acquire))
+                != 0;
+        });
         ok = known == 1 && mt_same_position(ah->start, *rng);
     }
     if (!ok) {
@@ -3921,12 +3924,31 @@ static int64_t mh_ahead_adopt(bnpc_ctx *c, bnpc_mt19937 *rng, int64_t G,
         return 0;
     }
     const int64_t rows = std::min<int64_t>(ah->rows, G);
-    while (ah->rows_ready.load(std::memory_order_acquire) < rows)
-        __builtin_ia32_pause();
-    *rng = ah->after_row[(size_t)(rows - 1)];
-    mh_ahead_drop(c);
     c->ahead_taken++;
     c->ahead_rows_taken += rows;
+    return rows;
+}
+
+// returns when the walker has published its rows up to n
+static void mh_ahead_wait_rows(const MhAhead *ah, int64_t n)
+{
+    bnpc_spin_until([&] {
+        return ah->rows_ready.load(std::memory_order_acquire) >= n;
+    });
+}
+
+// A small batch (the rows of a restricted scan) takes a walker's rows whole:
+// the number adopted (the live stream then stands behind them), 0 if there is
+// no walker or the live stream stands elsewhere.
+static int64_t mh_ahead_adopt(bnpc_ctx *c, bnpc_mt19937 *rng, int64_t G,
+                              int64_t M, int64_t n_sd)
+{
+    const int64_t rows = mh_ahead_claim(c, true, rng, G, M, n_sd);
+    if (rows) {
+        mh_ahead_wait_rows(c->ahead, rows);
+        *rng = c->ahead->after_row[(size_t)(rows - 1)];
+        mh_ahead_drop(c);
+    }
     return rows;
 }
 
@@ -4303,31 +4325,13 @@ static int mh_batch_dev_impl(bnpc_ctx *c, const bnpc_host_kernels *k,
     // Draws taken ahead (MhAhead above): adopted iff the live stream stands
     // where the walker's stood when it began to draw.
     MhAhead *ah = c->ahead;
-    int64_t ahead_rows = 0;
-    if (ah && ah->active) {
-        bool ok = rng && row0 == 0 && G_all < 0 && counts_src == 0
-            && ah->M == M && ah->n_sd == a->n_sd && c->tun.mh_ahead != 3;
-        if (ok) {
-            int known;
-            while ((known = ah->start_known.load(std::memory_order_acquire))
-                   == 0)
-                __builtin_ia32_pause();
-            ok = known == 1 && mt_same_position(ah->start, *rng);
-        }
-        if (!ok) {
-            mh_ahead_drop(c);
-        } else {
-            ahead_rows = std::min<int64_t>(ah->rows, G);
-            c->ahead_taken++;
-            c->ahead_rows_taken += ahead_rows;
-        }
-    }
+    const int64_t ahead_rows = mh_ahead_claim(
+        c, row0 == 0 && G_all < 0 && counts_src == 0, rng, G, M, a->n_sd);
     // the walker's part of the batch is over: the live stream continues from
     // the state kept after the last row taken from it
     auto ahead_close = [&]() {
         if (!ahead_rows || !ah->active) return;
-        while (ah->rows_ready.load(std::memory_order_acquire) < ahead_rows)
-            __builtin_ia32_pause();
+        mh_ahead_wait_rows(ah, ahead_rows);
         *rng = ah->after_row[(size_t)(ahead_rows - 1)];
         mh_ahead_drop(c);
     };
@@ -4360,8 +4364,7 @@ static int mh_batch_dev_impl(bnpc_ctx *c, const bnpc_host_kernels *k,
             const int64_t hi = g0 + Gp;
             if (lo < ahead_rows) {      // rows the walker took (or is taking)
                 const int64_t upto = std::min(hi, ahead_rows);
-                while (ah->rows_ready.load(std::memory_order_acquire) < upto)
-                    __builtin_ia32_pause();
+                mh_ahead_wait_rows(ah, upto);
                 lo = upto;
             }
             if (lo < hi) {              // rows this thread draws
@@ -4436,14 +4439,12 @@ static int mh_batch_dev_impl(bnpc_ctx *c, const bnpc_host_kernels *k,
             int p = 0;
             while (p + 1 < parts && g >= cut[p + 1]) p++;
             if (ready.load(std::memory_order_acquire) > p) return true;
-            for (long spins = 0;; spins++) {
-                if (failed.load(std::memory_order_relaxed)) return false;
-                if (issued.load(std::memory_order_acquire) > p
-                    && (int)(*word - done_seq[p]) >= 0)
-                    break;
-                if (spins < 4000) __builtin_ia32_pause();
-                else std::this_thread::yield();
-            }
+            bnpc_spin_until([&] {
+                return failed.load(std::memory_order_relaxed)
+                    || (issued.load(std::memory_order_acquire) > p
+                        && (int)(*word - done_seq[p]) >= 0);
+            }, 4000);
+            if (failed.load(std::memory_order_relaxed)) return false;
             std::atomic_thread_fence(std::memory_order_acquire);
             int seen = ready.load(std::memory_order_relaxed);
             while (seen < p + 1

@@ -220,13 +220,6 @@ static const double *dominated_bounds(int64_t A)
 // parallel, their SUMS stay sequential in index order (same bits).
 namespace {
 
-inline void spin_pause()
-{
-#if defined(__x86_64__)
-    __builtin_ia32_pause();
-#endif
-}
-
 struct ParScan {
     enum { SCAN = 1, EXP_TAIL = 2, EXP_PROB = 3, EXIT = 4, MAXT = 64 };
     int T = 1;
@@ -289,7 +282,9 @@ struct ParScan {
         done.store(0, std::memory_order_relaxed);
         phase.fetch_add(1, std::memory_order_release);
         work(0);
-        while (done.load(std::memory_order_acquire) != T - 1) spin_pause();
+        // (the phase waits never yield: the ranks are held for this window)
+        while (done.load(std::memory_order_acquire) != T - 1)
+            bnpc_cpu_relax();
     }
     void finish()
     {
@@ -303,7 +298,7 @@ struct ParScan {
         for (;;) {
             uint32_t p;
             while ((p = phase.load(std::memory_order_acquire)) == seen)
-                spin_pause();
+                bnpc_cpu_relax();
             seen = p;
             if (mode == EXIT) return;
             work(rank);

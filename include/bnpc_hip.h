@@ -22,8 +22,12 @@
  *     use it - bnpc_mh_batch, bnpc_log_accept, bnpc_beta_logpdf_f32,
  *     bnpc_gibbs_sweep, bnpc_rg_scan_step - may be called from several host
  *     threads at once (each on its own context / buffers): they take turns
- *     on the team, one job at a time.  The team is rebuilt in a fork()ed
- *     child on first use; a child must not be forked WHILE a call is running.
+ *     on the team, one job at a time.  The same holds for the process's ONE
+ *     aside thread, on which bnpc_chain_step, bnpc_rg_scan_step and
+ *     bnpc_sm_move post the walker that takes a parameter batch's draws
+ *     ahead: posters take turns on it, one job at a time.  The team and the
+ *     aside are rebuilt in a fork()ed child on first use; a child must not be
+ *     forked WHILE a call is running.
  *   - floating point: tables, accumulators and outputs are float64; theta is
  *     float32 and (1 - theta) is evaluated in float32, as in the reference.
  *

@@ -591,6 +591,10 @@ def test_host_threads_are_divided_among_chains_sharing_a_gpu(monkeypatch):
     assert os.environ['BNPC_HOST_SHARE'] == '8'
     assert os.environ['BNPC_HOST_SPIN_US'] == '5'
     assert _lib.host_threads() == 1
+    # a value of the user's is read as the library reads it: its leading
+    # integer
+    monkeypatch.setenv('BNPC_HOST_SPIN_US', '5.0')
+    assert _lib.host_settings(8, 2)['spin_us'] == 5
     monkeypatch.delenv('BNPC_HOST_SPIN_US')
     monkeypatch.setattr(os, 'sched_getaffinity', lambda pid: set(range(128)))
     monkeypatch.setattr(os, 'cpu_count', lambda: 256)

@@ -476,6 +476,21 @@ def batch(jobs, tasks, ranks, seed):
 jobs = int(sys.argv[1])
 for ranks in (1, 2, 3, 16, 64):
     batch(jobs, 64, ranks, ranks)
+# four posters at once (ctypes drops the GIL): they take turns on the team
+# and on the aside thread
+import threading
+errors = []
+def poster(seed):
+    try:
+        batch(jobs // 4, 64, 16, seed)
+    except BaseException as err:
+        errors.append(err)
+threads = [threading.Thread(target=poster, args=(50 + i,)) for i in range(4)]
+for t in threads:
+    t.start()
+for t in threads:
+    t.join()
+assert not errors, errors
 # a fork() between batches: the child builds a team of its own
 pid = os.fork()
 if pid == 0:
@@ -496,9 +511,10 @@ print('ok')
 def test_thread_team_stress(spin_us):
     """10^4 jobs (BNPC_STRESS_JOBS; the 10^5 runs are logged under
     profiles/r03) of 1-64 tasks per rank count 1 / 2 / 3 / 16 / 64 (the team
-    grows in place), tiny jobs back to back, a fork() in between, with and
-    without the spin before a worker parks (BNPC_HOST_SPIN_US): every task
-    runs exactly once and nothing hangs (the lost
+    grows in place), tiny jobs back to back, then from four host threads at
+    once (posters take turns on the team and on the aside thread), a fork()
+    in between, with and without the spin before a worker parks
+    (BNPC_HOST_SPIN_US): every task runs exactly once and nothing hangs (the lost
     wake-up of dd42c54 would hang here)."""
     import subprocess
     import sys
