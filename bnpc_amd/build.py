@@ -8,6 +8,8 @@ import sys
 PKG = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(PKG)
 SOURCES = [os.path.join(PKG, 'csrc', 'bnpc_kernels.hip'),
+    os.path.join(PKG, 'csrc', 'bnpc_context.cpp'),
+    os.path.join(PKG, 'csrc', 'bnpc_mhbatch.cpp'),
     os.path.join(PKG, 'csrc', 'bnpc_sweeps.cpp'),
     os.path.join(PKG, 'csrc', 'bnpc_moves.cpp'),
     os.path.join(PKG, 'csrc', 'bnpc_step.cpp'),
@@ -16,7 +18,8 @@ SOURCES = [os.path.join(PKG, 'csrc', 'bnpc_kernels.hip'),
     os.path.join(PKG, 'csrc', 'bnpc_ingest.cpp'),
     os.path.join(PKG, 'csrc', 'bnpc_codist.hip')]
 HEADERS = [os.path.join(ROOT, 'include', 'bnpc_hip.h'),
-    os.path.join(PKG, 'csrc', 'bnpc_internal.h')]
+    os.path.join(PKG, 'csrc', 'bnpc_internal.h'),
+    os.path.join(PKG, 'csrc', 'bnpc_ctx.h')]
 TARGET = os.path.join(PKG, 'libbnpc_hip.so')
 # BNPC_SANITIZE=thread|address,undefined builds the HOST side instrumented
 # into build/libbnpc_hip.<sanitizer>.so (git- AND gpurun-ignored: CPU runs

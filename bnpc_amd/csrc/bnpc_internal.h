@@ -114,7 +114,7 @@ bool bnpc_aside_start(const std::function<void()> &fn);
 void bnpc_aside_wait();
 #endif
 
-// bnpc_kernels.hip: the {ones, zeros} 64-bit words of one cell's row
+// bnpc_context.cpp: the {ones, zeros} 64-bit words of one cell's row
 // (W pairs), or NULL
 const unsigned long long *bnpc_ctx_row(const bnpc_ctx *c, int64_t cell,
                                        int64_t *M, int *W);
@@ -139,7 +139,7 @@ int bnpc_sweep_open_cluster(bnpc_gibbs_state *st, bnpc_mt19937 *rng,
 double bnpc_legacy_gamma(bnpc_mt19937 *rng, bnpc_legacy_gauss *g, double shape,
                          double scale);
 
-// bnpc_kernels.hip: counts of the two launch clusters of a restricted scan +
+// bnpc_mhbatch.cpp: counts of the two launch clusters of a restricted scan +
 // the (screened) parameter batch on one stream synchronisation
 // The next screened bnpc_mh_batch of this thread has its rank 0 call *hook
 // before it joins the evaluation of the batch (bnpc_mh_batch_dev: the draws
@@ -152,7 +152,7 @@ void bnpc_mh_rank0_hook(const std::function<void()> *hook);
 // false gives the batch up.  NULL: nothing.  Consumed by that call.
 void bnpc_mh_row_gate(const std::function<bool(int64_t)> *gate);
 #ifdef __cplusplus
-// bnpc_kernels.hip: the draws of the NEXT screened parameter batch on this
+// bnpc_mhbatch.cpp: the draws of the NEXT screened parameter batch on this
 // context taken ahead (MhAhead there): a walker on the aside thread takes a
 // copy of (rng, g), runs `prelude` on it - the draws the stream goes through
 // before the batch begins; false: it cannot tell - and then draws `rows` rows

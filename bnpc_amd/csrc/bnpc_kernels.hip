@@ -1,5 +1,11 @@
-// bnpc_kernels.hip - gfx950 (MI355X, CDNA4) kernels and the device half of the
-// C-ABI declared in include/bnpc_hip.h.
+// bnpc_kernels.hip - gfx950 (MI355X, CDNA4) kernels of the C-ABI declared in
+// include/bnpc_hip.h, and every host function that launches one: the gather
+// of a view's lane masks, the likelihood launches (issue_ll / launch_ll /
+// issue_seqp / ll_common) and the calls built on them, hints, rows, tables,
+// counts, the parameter batch's screen (mh_screen_launch), the total, and the
+// bench / timer entry points.  The context they work on, its pinned memory and
+// completion words are bnpc_context.cpp's (bnpc_ctx.h); the screened
+// parameter batch that drives mh_screen_launch is bnpc_mhbatch.cpp's.
 //
 // Design (DESIGN.md sections 3-4), written for wave64 / CDNA4, no MFMA:
 //
@@ -25,55 +31,15 @@
 
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
-#include <atomic>
-#include <thread>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 #include <math.h>
-#include <sys/mman.h>
-#include <time.h>
-#include <mutex>
 #include <vector>
 #include <algorithm>
 
-#include "bnpc_hip.h"
-#include "bnpc_internal.h"
-
-// ---------------------------------------------------------------------------
-// error plumbing
-// ---------------------------------------------------------------------------
-static thread_local char g_err[512] = "";
-
-void bnpc_set_error(const char *fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-}
-
-extern "C" const char *bnpc_last_error(void) { return g_err; }
-extern "C" int bnpc_abi_version(void) { return 12; }
-
-#define HIPCHK(expr)                                                         \
-    do {                                                                     \
-        hipError_t e_ = (expr);                                              \
-        if (e_ != hipSuccess) {                                              \
-            bnpc_set_error("%s failed: %s (%s:%d)", #expr,                   \
-                           hipGetErrorString(e_), __FILE__, __LINE__);       \
-            return 1;                                                        \
-        }                                                                    \
-    } while (0)
-
-#define ARGCHK(cond, msg)                                                    \
-    do {                                                                     \
-        if (!(cond)) {                                                       \
-            bnpc_set_error("bad argument: %s", msg);                         \
-            return 2;                                                        \
-        }                                                                    \
-    } while (0)
+#include "bnpc_ctx.h"
 
 // ---------------------------------------------------------------------------
 // per-launch device timers (bnpc_launch_timers: bench.py's
@@ -114,613 +80,6 @@ static LaunchTimers g_timers;
         else                                                                  \
             hipLaunchKernelGGL(kern, grid, block, lds, stream, __VA_ARGS__);  \
     } while (0)
-
-// ---------------------------------------------------------------------------
-// context
-// ---------------------------------------------------------------------------
-struct DevBuf {
-    void *p = nullptr;
-    size_t cap = 0;
-};
-
-struct View {
-    DevBuf masks;       // ulonglong2 [nblk][Mpad]
-    int64_t n = 0;      // slots in use
-    int64_t nblk = 0;
-};
-
-// Switches, read from the environment when a context is created and again
-// by bnpc_reload_options (tests); never on the launch path.  README lists
-// them; the tuning constants that used to be switches (chunking of split
-// launches, zero-copy sizes, the screen's minimum batch ...) are the measured
-// values below.
-struct Tunables {
-    int msplit = 1;                 // BNPC_MSPLIT: mutation-split small launches
-    int force_kw = 0;               // BNPC_KW: force the cluster tile (tests)
-    int zero_copy = 1;              // BNPC_ZERO_COPY: small payloads are read /
-                                    // written in place in pinned host memory
-    int mask_counts_max = 64;       // BNPC_MASK_COUNTS_MAX: segments for the
-                                    // mask-popcount counts (tests lower it)
-    int mh_screen = 1;              // BNPC_MH_SCREEN: device screen of the
-                                    // parameter batches
-    int done_words = 1;             // BNPC_DONE_WORDS: completion words written
-                                    // by the kernels (0: stream synchronisation)
-    int msplit_chunks = 0;          // BNPC_MSPLIT = N >= 2: force the chunk count
-                                    // of split launches (tools/msplit_sweep.py)
-    int screen_theta = 1;           // BNPC_MH_SCREEN = 2: verdicts only - not the
-                                    // float32 bits of the proposals it accepts
-    int mh_ahead = 1;               // BNPC_MH_AHEAD: the draws of the next
-                                    // parameter batch taken ahead on the aside
-                                    // thread (0: never; 2: for a batch of any
-                                    // size - tests; 3: taken and then thrown
-                                    // away - tests of the discard path)
-    size_t mh_pin_max = (size_t)512 << 20;  // pinned block of a screened
-                                    // parameter batch at most: twice
-                                    // BNPC_SWEEP_BYTES, the host budget of a
-                                    // sweep's matrix (default 256 MiB -> 512:
-                                    // 37 bytes per entry, 14.5 M entries -
-                                    // config 4's K0 x M batch fits, config 5's
-                                    // 158 M are screened in slices of rows
-                                    // that reuse the block)
-};
-
-#define MSPLIT_MAX 64               // chunks of a split launch at most
-#define ASM2_MIN_WGS 448            // workgroups from which a wave takes 2 blocks
-#define TABLES_FLAT_MAX (1 << 20)   // table elements up to which one thread
-                                    // builds one element
-#define ZC_IN_MAX ((int64_t)256 << 10)      // zero-copy inputs / results up to
-#define ZC_OUT_MAX ((int64_t)512 << 10)
-#define MH_SCREEN_MIN 512           // batch entries from which the screen pays
-#define MH_THREADED_MIN 65536       // batch entries from which rank 0 issues
-                                    // draws and launches ahead of the waits
-                                    // (the pinned block of a screened batch
-                                    // is at most Tunables::mh_pin_max bytes)
-#define MH_PIN_NO_MEMORY 77         // mh_pin_get: the host refused the block
-#define MH_AHEAD_MIN 8192           // batch entries from which its draws are
-                                    // taken ahead (config 3's 10-16 thousand:
-                                    // parameters 0.102 -> 0.090 ms, five
-                                    // interleaved pairs, profiles/r06/
-                                    // c3_walker_ab; config 2's 2000 cost less
-                                    // than the hand-over)
-#define MH_AHEAD_SCAN_MIN 2048      // ... of a restricted scan's batch (2-3 rows:
-                                    // the walker has the scan's sums and loop,
-                                    // 50 us and more, for 10-35 us of draws)
-#define MH_AHEAD_MAX_ROWS 1024      // ... and rows up to which (a stream state
-                                    // is kept per row: 2.5 KB)
-#define HINT_COLS_MAX 32767         // columns of a hinted sweep (int16 in the
-                                    // record)
-#define HINT_THROUGH_MAX 1024       // ... up to which rows that will be scanned
-                                    // are written through to the host
-#define LDS_TABLE_MIN_M 3072        // k_ll8_lds: mutations (padded) from which,
-#define LDS_TABLE_MIN_WGS 4096      // ... and workgroups from which it wins
-
-static int env_int(const char *name, int dflt)
-{
-    const char *e = getenv(name);
-    return e ? atoi(e) : dflt;
-}
-
-static void read_tunables(Tunables &t)
-{
-    t.msplit = env_int("BNPC_MSPLIT", 1);
-    t.force_kw = env_int("BNPC_KW", 0);
-    if (t.force_kw != 1 && t.force_kw != 2 && t.force_kw != 4
-        && t.force_kw != 8)
-        t.force_kw = 0;
-    t.zero_copy = env_int("BNPC_ZERO_COPY", 1);
-    t.mask_counts_max = env_int("BNPC_MASK_COUNTS_MAX", 64);
-    t.mh_screen = env_int("BNPC_MH_SCREEN", 1);
-    t.done_words = env_int("BNPC_DONE_WORDS", 1);
-    t.screen_theta = t.mh_screen != 2;
-    t.mh_ahead = env_int("BNPC_MH_AHEAD", 1);
-    {
-        const char *e = getenv("BNPC_SWEEP_BYTES");
-        const long long b = e ? atoll(e) : 0;
-        t.mh_pin_max = 2 * (size_t)(b > 0 ? b : (long long)256 << 20);
-    }
-    t.msplit_chunks = t.msplit >= 2 ? t.msplit : 0;
-}
-
-#define DONE_SLOTS 3     // 0, 1: the launches of a call; 2: the deferred total
-// what a kernel needs to tell the host that it is done (signal_done below)
-struct DoneSignal {
-    unsigned *count;    // device word, zero between launches
-    unsigned *flag;     // pinned host word (device address)
-    unsigned seq;
-};
-
-// the column priors of a hint launch of up to 64 columns (kernel argument)
-struct Top2Prior {
-    double v[64];
-};
-
-struct bnpc_ctx {
-    Tunables tun;
-    int device = 0;
-    int64_t N = 0, M = 0;
-    int W = 0;          // 64-bit words per row
-    int Mpad = 0;       // W * 64
-    int Mt = 0;         // table row count per group: M rounded up to 8
-    hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    ulonglong2 *rows = nullptr;           // [N][W]
-    std::vector<ulonglong2> host_rows;    // the same words on the host: the
-                                          // observations of ONE cell shape the
-                                          // Beta draws of a cluster it opens
-    std::vector<int32_t> cell_n1, cell_n0;
-    View views[BNPC_MAX_VIEWS];
-    // scratch
-    DevBuf theta, tabs, tab_in, out, cells, chunks, cnt, partial, part;
-    DevBuf theta_store, row_idx;    // resident parameter rows + selection
-    int64_t store_rows = 0;
-    const long long *use_rows = nullptr;    // non-null: tables from the store
-    // resident per-cluster counts of the last bnpc_colcounts_by_label
-    DevBuf lab_cnt;
-    int64_t lab_K = 0;
-    uint64_t lab_gen = 0;       // bumped by every bnpc_colcounts_by_label
-    int64_t cnt_rows = 0;       // segments of the last bnpc_view_counts (c->cnt)
-    // pinned host buffers: the sweep's ll matrix / small reductions
-    void *pin = nullptr;
-    size_t pin_cap = 0;
-    void *pin_small = nullptr;
-    // side lane: a second stream with its own scratch, used by the small
-    // synchronous calls (one column for a cluster opened mid-sweep) while an
-    // issued tile occupies the main stream - they must not queue behind it
-    hipStream_t side_stream = nullptr;
-    DevBuf side_theta, side_tabs, side_out, side_part;
-    // pinned staging arena for small host <-> device payloads (parameter
-    // rows, cell lists, counts): a copy from/to pinned memory is a plain DMA
-    // enqueue, a copy from/to pageable memory is staged by the runtime at
-    // ~10 us apiece.  Reset at the start of every call that uses it; every
-    // such call ends with a stream synchronisation.
-    void *stage = nullptr;
-    char *stage_dev = nullptr;      // the arena as the device addresses it
-    size_t stage_used = 0;
-    // small results written by kernels straight into pinned host memory
-    void *zc_out = nullptr;
-    char *zc_out_dev = nullptr;
-    void *hint_pin = nullptr;       // the sweep's per-cell hints (pinned)
-    size_t hint_cap = 0;
-    DevBuf hint_prior;              // priors of a hinted sweep with > 64 columns
-    void *hint_prior_pin = nullptr; // ... staged here (pinned, HINT_COLS_MAX)
-    // bnpc_ll_theta_pinned_sums_issue: a hinted sweep whose hint kernel is
-    // launched later (bnpc_hints_in_order_issue), when the caller has drawn
-    // its visiting order under the sums - what that launch needs
-    struct {
-        // 0: no sums issued; 1: issued, the hint kernel is to be launched;
-        // 2: issued without a hint buffer (the matrix was copied instead)
-        int state = 0;
-        int64_t n = 0, K = 0, ldo = 0;
-        size_t bytes = 0;
-        Top2Prior prior;            // K <= 64 (more: c->hint_prior)
-        void *hint_dev = nullptr;
-        double *rows_dev = nullptr;
-    } hint_later;
-    void *order_pin = nullptr;      // the visiting order, pinned (N entries)
-    DevBuf order_dev;               // ... and on the device
-    // pinned block of a screened parameter batch (bnpc_mh_batch_dev): the
-    // draws, the old parameter rows and the screen's verdicts, read / written
-    // in place by k_mh_screen
-    void *mh_pin = nullptr;
-    char *mh_dev = nullptr;
-    size_t mh_cap = 0;
-    size_t mh_capE = 0;             // entries the block is laid out for
-    struct MhAhead *ahead = nullptr;    // draws taken ahead (bnpc_mh_ahead_*)
-    int64_t ahead_begun = 0, ahead_taken = 0, ahead_rows_taken = 0;
-    double mh_flagged_share = 0.25; // host work the last screened batch left,
-                                    // per entry (sizes the next one's team)
-    hipEvent_t mh_ev[2] = {};
-    int64_t screened = 0, screen_kept = 0;  // elements seen / left to the host
-    size_t pin_lazy_bytes = 0;      // sweep matrix still on the device (c->out)
-    // ... unless the previous hinted sweep had to fetch it: then the copy is
-    // queued right behind the hint kernel and lands while the host prepares
-    // the sweep (a running chain scans ~9 % of its cells: it always needs it;
-    // a settled one never does)
-    bool matrix_eager = false, lazy_fetched = false, pin_copy_queued = false;
-    hipEvent_t ev_hints = nullptr;
-    // completion words (DoneSignal): two slots, so that two launches of one
-    // call may be in flight (the two halves of a screened batch)
-    unsigned *done_count = nullptr;         // device, DONE_SLOTS words
-    unsigned *done_pin = nullptr;           // pinned host, DONE_SLOTS x 16 words
-    unsigned *done_dev = nullptr;           // ... as the device addresses it
-    unsigned done_seq = 0;
-    unsigned total_seq = 0;                 // of the pending bnpc_ll_total
-    int total_slot = -1;
-    DoneSignal sig_next = {nullptr, nullptr, 0};    // for the last kernel of
-    bool sig_attached = false;                      // the next issue_ll
-    // bnpc_ll_theta_begin / _end: an evaluation whose result is written in
-    // place for the host and picked up later (the caller works in between)
-    bool defer_next = false, defer_set = false;
-    struct {
-        void *zc_host;
-        unsigned seq;
-        double *out;
-        size_t bytes;
-        int64_t n, K, ldo;
-    } defer = {nullptr, 0, nullptr, 0, 0, 0, 0};
-    // bnpc_view_set's own pinned cell list (N entries) and the event that
-    // says the last gather has read it
-    void *view_cells_pin = nullptr;
-    const long long *view_cells_dev = nullptr;
-    hipEvent_t view_cells_read = nullptr;
-    bool view_cells_busy = false;
-    bool total_pending = false;     // a deferred bnpc_ll_total_issue
-    int total_blocks = 0, total_E = 0;
-    // where the kernels of the current call read their inputs from: device
-    // scratch filled by a DMA copy, or the staging arena in place
-    const float *theta_src = nullptr;
-    const double *tab_src = nullptr;
-    const long long *cells_src = nullptr;
-    // Issued (asynchronous) tiles: up to BNPC_TILE_SLOTS in flight, each with
-    // its own pinned result buffer.  The sums of consecutive tiles alternate
-    // between two device buffers and the copy to the host runs on its own
-    // stream, so the copy of one tile overlaps the sums of the next.
-    void *tile_pin[BNPC_TILE_SLOTS] = {};
-    size_t tile_cap[BNPC_TILE_SLOTS] = {};
-    size_t tile_bytes[BNPC_TILE_SLOTS] = {};
-    void *tile_rows[BNPC_TILE_SLOTS] = {};      // pinned staging of the ids
-    size_t tile_rows_cap[BNPC_TILE_SLOTS] = {};
-    void *tile_cells[BNPC_TILE_SLOTS] = {};     // ... and of the tile's cells
-    size_t tile_cells_cap[BNPC_TILE_SLOTS] = {};
-    void *tile_hint[BNPC_TILE_SLOTS] = {};      // pinned: the tile's hints
-    size_t tile_hint_cap[BNPC_TILE_SLOTS] = {};
-    void *tile_prior[BNPC_TILE_SLOTS] = {};     // pinned staging of the priors
-    size_t tile_prior_cap[BNPC_TILE_SLOTS] = {};
-    bool tile_hinted[BNPC_TILE_SLOTS] = {};
-    DevBuf tile_prior_dev[2];                   // by parity, like tile_out
-    hipEvent_t tile_done[BNPC_TILE_SLOTS] = {}; // copy landed in tile_pin
-    bool tile_pending[BNPC_TILE_SLOTS] = {};
-    DevBuf tile_out[2];                         // by parity of the issue count
-    hipEvent_t tile_summed[2] = {};             // sums written to tile_out
-    hipEvent_t tile_out_free[2] = {};           // its last copy has left
-    uint64_t tile_seq = 0;
-    hipStream_t copy_stream = nullptr;
-    bool any_tile_pending() const
-    {
-        for (bool p : tile_pending)
-            if (p) return true;
-        return false;
-    }
-    // configuration of the last k_ll launch (bnpc_bench_ll re-issues it)
-    int last_kw = 0, last_view = -1, last_ms = 1, last_mchunk = 0;
-    int64_t last_K = 0, last_ldo = 0;
-    double *last_out = nullptr;
-    double *dst_override = nullptr; // device-addressable result buffer
-    bool last_from_theta = false;
-    double last_FP = 0.0, last_FN = 0.0;
-    char last_name[96] = "";
-};
-
-static void mh_ahead_destroy(bnpc_ctx *c);      // (with MhAhead, below)
-
-static int ensure(DevBuf &b, size_t bytes)
-{
-    if (bytes <= b.cap) return 0;
-    if (b.p) HIPCHK(hipFree(b.p));
-    b.p = nullptr;
-    b.cap = 0;
-    size_t cap = bytes + bytes / 4 + 256;
-    HIPCHK(hipMalloc(&b.p, cap));
-    b.cap = cap;
-    return 0;
-}
-
-// Large pinned host buffers (result matrices, tiles: hundreds of MiB).
-// hipHostMalloc pins 4 KiB pages - 45-48 ms per 300 MiB on the MI355X host,
-// and a first sweep needs two or three of them.  Anonymous memory on
-// transparent huge pages, touched and then registered, costs 17 + 1 ms for the
-// same size and is the same DMA target (57 GB/s either way;
-// tools/ubench/pin_probe.hip).  Falls back to hipHostMalloc when huge pages
-// are switched off (4 KiB pages would make this route the slower one) or
-// anything fails.  `cap` identifies the route at release time: huge-page
-// buffers have a capacity that is a multiple of 2 MiB and are remembered.
-#define PIN_HUGE_MIN ((size_t)16 << 20)
-#define PIN_HUGE_ALIGN ((size_t)2 << 20)
-
-static bool thp_available()
-{
-    static const bool ok = [] {
-        FILE *f = fopen("/sys/kernel/mm/transparent_hugepage/enabled", "r");
-        if (!f) return false;
-        char line[128] = {0};
-        const bool got = fgets(line, sizeof line, f) != nullptr;
-        fclose(f);
-        return got && !strstr(line, "[never]");
-    }();
-    return ok;
-}
-
-static std::vector<void *> &huge_pins()
-{
-    static std::vector<void *> v;
-    return v;
-}
-
-static std::mutex &huge_pins_lock()         // contexts may live on threads
-{
-    static std::mutex m;
-    return m;
-}
-
-static int pinned_alloc(void **out, size_t *cap, size_t bytes)
-{
-    *out = nullptr;
-    *cap = 0;
-    if (bytes >= PIN_HUGE_MIN && thp_available()) {
-        const size_t len = (bytes + PIN_HUGE_ALIGN - 1) & ~(PIN_HUGE_ALIGN - 1);
-        char *raw = (char *)mmap(nullptr, len + PIN_HUGE_ALIGN,
-                                 PROT_READ | PROT_WRITE,
-                                 MAP_PRIVATE | MAP_ANONYMOUS, -1, 0);
-        if (raw != (char *)MAP_FAILED) {
-            char *p = (char *)(((uintptr_t)raw + PIN_HUGE_ALIGN - 1)
-                               & ~(uintptr_t)(PIN_HUGE_ALIGN - 1));
-            if (p > raw) munmap(raw, (size_t)(p - raw));
-            const size_t tail = (size_t)(raw + len + PIN_HUGE_ALIGN - (p + len));
-            if (tail) munmap(p + len, tail);
-            (void)madvise(p, len, MADV_HUGEPAGE);
-            // fault the huge pages in before pinning: one touch per 2 MiB
-            // (the kernel zeroes them; anything left on small pages is
-            // faulted in by the registration itself)
-            for (size_t off = 0; off < len; off += PIN_HUGE_ALIGN)
-                ((volatile char *)p)[off] = 0;
-            if (hipHostRegister(p, len, hipHostRegisterDefault) == hipSuccess) {
-                std::lock_guard<std::mutex> hold(huge_pins_lock());
-                huge_pins().push_back(p);
-                *out = p;
-                *cap = len;
-                return 0;
-            }
-            (void)hipGetLastError();
-            munmap(p, len);
-        }
-    }
-    HIPCHK(hipHostMalloc(out, bytes, hipHostMallocDefault));
-    *cap = bytes;
-    return 0;
-}
-
-static void pinned_free(void *p, size_t cap)
-{
-    if (!p) return;
-    bool huge = false;
-    {
-        std::lock_guard<std::mutex> hold(huge_pins_lock());
-        std::vector<void *> &v = huge_pins();
-        auto it = std::find(v.begin(), v.end(), p);
-        if (it != v.end()) {
-            v.erase(it);
-            huge = true;
-        }
-    }
-    if (huge) {
-        (void)hipHostUnregister(p);
-        munmap(p, cap);
-    } else {
-        (void)hipHostFree(p);
-    }
-}
-
-#define STAGE_BYTES ((size_t)4 << 20)
-#define ZC_OUT_BYTES ((size_t)1 << 20)
-
-// a slot of the staging arena, or nullptr when the payload is too large
-static void *stage_slot(bnpc_ctx *c, size_t bytes)
-{
-    if (!c->stage) {
-        if (hipHostMalloc(&c->stage, STAGE_BYTES, hipHostMallocDefault)
-                != hipSuccess) {
-            c->stage = nullptr;
-            return nullptr;
-        }
-        void *dev = nullptr;
-        if (hipHostGetDevicePointer(&dev, c->stage, 0) == hipSuccess)
-            c->stage_dev = (char *)dev;
-    }
-    const size_t at = (c->stage_used + 255) & ~(size_t)255;
-    if (at + bytes > STAGE_BYTES) return nullptr;
-    c->stage_used = at + bytes;
-    return (char *)c->stage + at;
-}
-
-// Start of a call that stages inputs: the arena is free again - unless a
-// deferred total (bnpc_ll_total_issue) may still be reading its parameters
-// from it; then that kernel is waited for first (its result stays parked).
-static int arena_reset(bnpc_ctx *c)
-{
-    if (c->total_pending) HIPCHK(hipStreamSynchronize(c->stream));
-    c->stage_used = 0;
-    return 0;
-}
-
-// A DoneSignal for the next launch on slot 0 / 1 (the words are made on first
-// use; without them - or with BNPC_DONE_WORDS=0 - the signal is empty and the
-// caller synchronises as before).  *seq receives the number to wait for.
-static DoneSignal make_signal(bnpc_ctx *c, int slot, unsigned *seq)
-{
-    DoneSignal none = {nullptr, nullptr, 0};
-    *seq = 0;
-    if (!c->tun.done_words) return none;
-    if (!c->done_count) {
-        void *pin = nullptr, *dev = nullptr, *cnt = nullptr;
-        if (hipHostMalloc(&pin, DONE_SLOTS * 64, hipHostMallocDefault) != hipSuccess
-            || hipHostGetDevicePointer(&dev, pin, 0) != hipSuccess
-            || hipMalloc(&cnt, DONE_SLOTS * sizeof(unsigned)) != hipSuccess
-            || hipMemset(cnt, 0, DONE_SLOTS * sizeof(unsigned))
-                != hipSuccess) {
-            (void)hipGetLastError();
-            if (pin) (void)hipHostFree(pin);
-            if (cnt) (void)hipFree(cnt);
-            return none;
-        }
-        memset(pin, 0, DONE_SLOTS * 64);
-        c->done_pin = (unsigned *)pin;
-        c->done_dev = (unsigned *)dev;
-        c->done_count = (unsigned *)cnt;
-    }
-    if (++c->done_seq == 0) c->done_seq = 1;    // 0 = "no signal"
-    *seq = c->done_seq;
-    DoneSignal d = {c->done_count + slot, c->done_dev + 16 * slot, *seq};
-    return d;
-}
-
-// Wait for the word of a signalled launch; seq == 0 (no signal was attached)
-// or a word that does not come within the spin: hipStreamSynchronize.
-static int wait_done(bnpc_ctx *c, int slot, unsigned seq)
-{
-    if (seq) {
-        const volatile unsigned *f = c->done_pin + 16 * slot;
-        for (int spins = 0; spins < 20000; spins++) {       // ~100-200 us
-            // (launches of a stream finish in order and the numbers only
-            // grow: a later number on the word says this one is done too)
-            if ((int)(*f - seq) >= 0) {
-                std::atomic_thread_fence(std::memory_order_acquire);
-                return 0;
-            }
-            bnpc_cpu_relax();
-        }
-    }
-    HIPCHK(hipStreamSynchronize(c->stream));
-    return 0;
-}
-
-// Zero-copy input: the payload is copied into the pinned arena and the
-// kernels of this call read it there, over the host link, instead of from a
-// device buffer filled by a DMA copy - for payloads of a few hundred KiB a
-// copy engine launch costs more than the bytes.  Returns the DEVICE address,
-// or nullptr (too large / switched off): then the caller copies.  Every call
-// that uses the arena ends with a stream synchronisation.
-static const void *stage_in_place(bnpc_ctx *c, const void *src, size_t bytes)
-{
-    if (!c->tun.zero_copy || (int64_t)bytes > ZC_IN_MAX) return nullptr;
-    void *slot = stage_slot(c, bytes);
-    if (!slot || !c->stage_dev) return nullptr;
-    memcpy(slot, src, bytes);
-    return c->stage_dev + ((char *)slot - (char *)c->stage);
-}
-
-// Zero-copy output: `bytes` of pinned host memory the kernels of this call may
-// write their (small) result to; *dev receives the device address.  nullptr:
-// not available for this size.
-static void *zc_result(bnpc_ctx *c, size_t bytes, void **dev)
-{
-    if (!c->tun.zero_copy || (int64_t)bytes > ZC_OUT_MAX
-        || bytes > ZC_OUT_BYTES)
-        return nullptr;
-    if (!c->zc_out) {
-        if (hipHostMalloc(&c->zc_out, ZC_OUT_BYTES, hipHostMallocDefault)
-                != hipSuccess) {
-            c->zc_out = nullptr;
-            return nullptr;
-        }
-        void *d = nullptr;
-        if (hipHostGetDevicePointer(&d, c->zc_out, 0) != hipSuccess) {
-            (void)hipHostFree(c->zc_out);
-            c->zc_out = nullptr;
-            return nullptr;
-        }
-        c->zc_out_dev = (char *)d;
-    }
-    *dev = c->zc_out_dev;
-    return c->zc_out;
-}
-
-// host -> device on the context's stream; `src` may be released on return
-// only if the caller synchronises the stream before it returns itself
-static int h2d(bnpc_ctx *c, void *dst, const void *src, size_t bytes)
-{
-    void *slot = stage_slot(c, bytes);
-    if (slot) {
-        memcpy(slot, src, bytes);
-        src = slot;
-    }
-    HIPCHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, c->stream));
-    return 0;
-}
-
-// device -> host, completed by the caller's stream synchronisation followed
-// by d2h_finish (which moves the staged bytes to their destination)
-struct D2H {
-    void *dst, *slot;
-    size_t bytes;
-};
-
-static int d2h_begin(bnpc_ctx *c, D2H &t, void *dst, const void *src,
-                     size_t bytes)
-{
-    t.dst = dst;
-    t.bytes = bytes;
-    t.slot = stage_slot(c, bytes);
-    HIPCHK(hipMemcpyAsync(t.slot ? t.slot : dst, src, bytes,
-                          hipMemcpyDeviceToHost, c->stream));
-    return 0;
-}
-
-static void d2h_finish(const D2H &t)
-{
-    if (t.slot) memcpy(t.dst, t.slot, t.bytes);
-}
-
-static int ensure_pin(bnpc_ctx *c, size_t bytes)
-{
-    if (c->pin_copy_queued) {   // a queued copy still targets the buffer
-        HIPCHK(hipStreamSynchronize(c->stream));
-        c->pin_copy_queued = false;
-    }
-    c->pin_lazy_bytes = 0;      // a new request supersedes a matrix not fetched
-    if (bytes <= c->pin_cap) return 0;
-    pinned_free(c->pin, c->pin_cap);
-    c->pin = nullptr;
-    c->pin_cap = 0;
-    return pinned_alloc(&c->pin, &c->pin_cap, bytes + bytes / 4 + 4096);
-}
-
-// While a tile is in flight, run a call on the side lane: swap the stream and
-// the scratch buffers the likelihood path uses, restore on scope exit.
-struct SideLane {
-    bnpc_ctx *c;
-    bool on;
-    explicit SideLane(bnpc_ctx *ctx)
-        : c(ctx), on(ctx->side_stream && ctx->any_tile_pending())
-    {
-        if (on) flip();
-    }
-    ~SideLane()
-    {
-        if (on) flip();
-    }
-    void flip()
-    {
-        std::swap(c->stream, c->side_stream);
-        std::swap(c->theta, c->side_theta);
-        std::swap(c->tabs, c->side_tabs);
-        std::swap(c->out, c->side_out);
-        std::swap(c->part, c->side_part);
-    }
-};
-
-// the side lane, created at the first tile of a context: calls made while
-// tiles are in flight (a column for a cluster just opened, the columns of
-// clusters born since a tile was issued) run beside 10 ms kernels that fill
-// the chip; on a stream of the highest priority their few workgroups get the
-// next free slots instead of waiting for a whole tile.  (Compute units of
-// their own - the tile kernels on a CU-masked stream, the side lane on the
-// rest - were tried in round 4: the masked stream ran the whole sweep 12 %
-// slower, 0.53 against 0.475 s, for births that are bound by their host-side
-// Beta draws anyway.)
-static int ensure_lanes(bnpc_ctx *c)
-{
-    if (c->side_stream) return 0;
-    int least = 0, greatest = 0;
-    if (hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess
-        || hipStreamCreateWithPriority(&c->side_stream, hipStreamNonBlocking,
-                                       greatest) != hipSuccess) {
-        (void)hipGetLastError();        // no priorities here: a plain stream
-        c->side_stream = nullptr;
-        HIPCHK(hipStreamCreateWithFlags(&c->side_stream,
-                                        hipStreamNonBlocking));
-    }
-    return 0;
-}
 
 // ---------------------------------------------------------------------------
 // Completion words.  A converged step is a chain of small dependent launches
@@ -2176,36 +1535,10 @@ __global__ __launch_bounds__(256) void k_mh_screen(
 }
 
 // ---------------------------------------------------------------------------
-// host side of the C-ABI
+// host side: the launches
 // ---------------------------------------------------------------------------
-extern "C" int bnpc_device_count(int *count)
-{
-    ARGCHK(count, "count is NULL");
-    HIPCHK(hipGetDeviceCount(count));
-    return 0;
-}
-
-extern "C" int bnpc_device_info(int device, char *name, int len, int *cus)
-{
-    hipDeviceProp_t prop;
-    HIPCHK(hipGetDeviceProperties(&prop, device));
-    if (name && len > 0) {
-        strncpy(name, prop.gcnArchName, len - 1);
-        name[len - 1] = 0;
-    }
-    if (cus) *cus = prop.multiProcessorCount;
-    return 0;
-}
-
-extern "C" int bnpc_device_pci_bus_id(int device, char *bus_id, int len)
-{
-    ARGCHK(bus_id && len >= 16, "bus_id buffer too small");
-    HIPCHK(hipDeviceGetPCIBusId(bus_id, len, device));
-    return 0;
-}
-
-static int build_view(bnpc_ctx *c, int view, const long long *d_cells,
-                      int64_t n)
+// K1 over a view's cells (into the view's lane masks)
+int build_view(bnpc_ctx *c, int view, const long long *d_cells, int64_t n)
 {
     View &v = c->views[view];
     v.n = n;
@@ -2219,343 +1552,6 @@ static int build_view(bnpc_ctx *c, int view, const long long *d_cells,
                        c->rows, d_cells, (long long)n, c->W,
                        (ulonglong2 *)v.masks.p, c->Mpad);
     HIPCHK(hipGetLastError());
-    return 0;
-}
-
-// Context from ready bit planes: rows[N][W] of {ones, zeros} words (bits past
-// M clear, no bit set in both planes - checked).
-static int create_from_planes(int device, int64_t N, int64_t M,
-                              const ulonglong2 *rows, bnpc_ctx **out)
-{
-    HIPCHK(hipSetDevice(device));
-    bnpc_ctx *c = new bnpc_ctx();
-    read_tunables(c->tun);
-    c->device = device;
-    c->N = N;
-    c->M = M;
-    c->W = (int)((M + 63) / 64);
-    c->Mpad = c->W * 64;
-    c->Mt = (int)((M + 7) / 8 * 8);
-    c->cell_n1.assign(N, 0);
-    c->cell_n0.assign(N, 0);
-    const int tail_bits = (int)(M - (int64_t)(c->W - 1) * 64);  // 1..64
-    const unsigned long long tail_mask =
-        tail_bits == 64 ? ~0ull : ((1ull << tail_bits) - 1);
-    for (int64_t i = 0; i < N; i++) {
-        int32_t s1 = 0, s0 = 0;
-        const ulonglong2 *r = rows + (size_t)i * c->W;
-        for (int w = 0; w < c->W; w++) {
-            const unsigned long long ok = (w == c->W - 1) ? tail_mask : ~0ull;
-            if ((r[w].x & r[w].y) || ((r[w].x | r[w].y) & ~ok)) {
-                delete c;
-                bnpc_set_error("bit planes of row %lld are inconsistent",
-                               (long long)i);
-                return 2;
-            }
-            s1 += __builtin_popcountll(r[w].x);
-            s0 += __builtin_popcountll(r[w].y);
-        }
-        c->cell_n1[i] = s1;
-        c->cell_n0[i] = s0;
-    }
-
-#define CRCHK(expr)                                                          \
-    do {                                                                     \
-        hipError_t e_ = (expr);                                              \
-        if (e_ != hipSuccess) {                                              \
-            bnpc_set_error("%s failed: %s", #expr, hipGetErrorString(e_));   \
-            bnpc_destroy(c);                                                 \
-            return 1;                                                        \
-        }                                                                    \
-    } while (0)
-    const size_t bytes = (size_t)N * c->W * sizeof(ulonglong2);
-    c->host_rows.assign(rows, rows + (size_t)N * c->W);
-    CRCHK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
-    CRCHK(hipEventCreate(&c->ev0));
-    CRCHK(hipEventCreate(&c->ev1));
-    CRCHK(hipMalloc((void **)&c->rows, bytes));
-    CRCHK(hipMemcpyAsync(c->rows, rows, bytes, hipMemcpyHostToDevice,
-                         c->stream));
-    if (build_view(c, 0, nullptr, N)) {
-        bnpc_destroy(c);
-        return 1;
-    }
-    CRCHK(hipStreamSynchronize(c->stream));
-#undef CRCHK
-    *out = c;
-    return 0;
-}
-
-template <typename GetCode>
-static int create_impl(int device, int64_t N, int64_t M, GetCode code,
-                       bnpc_ctx **out)
-{
-    ARGCHK(out, "out is NULL");
-    ARGCHK(N > 0 && M > 0, "N and M must be positive");
-    ARGCHK(M < (1ll << 30) && N < (1ll << 40), "matrix too large");
-    *out = nullptr;
-    const int W = (int)((M + 63) / 64);
-    // pack on the host: 2 bits per entry
-    std::vector<ulonglong2> rows((size_t)N * W);
-    for (int64_t i = 0; i < N; i++) {
-        for (int w = 0; w < W; w++) {
-            unsigned long long o = 0, z = 0;
-            const int64_t m0 = (int64_t)w * 64;
-            const int64_t m1 = std::min<int64_t>(M, m0 + 64);
-            for (int64_t m = m0; m < m1; m++) {
-                const int v = code(i, m);
-                if (v == 1) o |= 1ull << (m - m0);
-                else if (v == 0) z |= 1ull << (m - m0);
-                else if (v != 3) {
-                    bnpc_set_error("data[%lld,%lld] is not 0, 1 or missing",
-                                   (long long)i, (long long)m);
-                    return 2;
-                }
-            }
-            rows[(size_t)i * W + w] = make_ulonglong2(o, z);
-        }
-    }
-    return create_from_planes(device, N, M, rows.data(), out);
-}
-
-extern "C" int bnpc_create_planes(int device, int64_t N, int64_t M,
-                                  const uint64_t *planes, bnpc_ctx **out)
-{
-    ARGCHK(out && planes, "NULL argument");
-    ARGCHK(N > 0 && M > 0, "N and M must be positive");
-    ARGCHK(M < (1ll << 30) && N < (1ll << 40), "matrix too large");
-    *out = nullptr;
-    return create_from_planes(device, N, M, (const ulonglong2 *)planes, out);
-}
-
-extern "C" int bnpc_create(int device, int64_t N, int64_t M,
-                           const double *data_nan, bnpc_ctx **out)
-{
-    ARGCHK(data_nan, "data is NULL");
-    return create_impl(device, N, M, [=](int64_t i, int64_t m) -> int {
-        const double v = data_nan[(size_t)i * M + m];
-        if (v != v) return 3;
-        if (v == 1.0) return 1;
-        if (v == 0.0) return 0;
-        return -1;
-    }, out);
-}
-
-extern "C" int bnpc_create_codes(int device, int64_t N, int64_t M,
-                                 const int8_t *codes, bnpc_ctx **out)
-{
-    ARGCHK(codes, "codes is NULL");
-    return create_impl(device, N, M, [=](int64_t i, int64_t m) -> int {
-        const int v = codes[(size_t)i * M + m];
-        return v == 2 ? 1 : v;      // 2 (homozygous) -> 1, dpmmIO.py:93
-    }, out);
-}
-
-extern "C" int bnpc_destroy(bnpc_ctx *c)
-{
-    if (!c) return 0;
-    (void)hipSetDevice(c->device);
-    if (c->stream) (void)hipStreamSynchronize(c->stream);
-    if (c->side_stream) (void)hipStreamSynchronize(c->side_stream);
-    if (c->copy_stream) (void)hipStreamSynchronize(c->copy_stream);
-    if (c->view_cells_pin) (void)hipHostFree(c->view_cells_pin);
-    if (c->view_cells_read) (void)hipEventDestroy(c->view_cells_read);
-    if (c->done_pin) (void)hipHostFree(c->done_pin);
-    if (c->done_count) (void)hipFree(c->done_count);
-    DevBuf *bufs[] = {&c->theta, &c->tabs, &c->tab_in, &c->out, &c->cells,
-                      &c->tile_out[0], &c->tile_out[1],
-                      &c->tile_prior_dev[0], &c->tile_prior_dev[1],
-                      &c->chunks, &c->cnt, &c->partial, &c->part,
-                      &c->lab_cnt, &c->theta_store, &c->row_idx,
-                      &c->side_theta, &c->side_tabs, &c->side_out,
-                      &c->side_part, &c->hint_prior, &c->order_dev};
-    for (DevBuf *b : bufs)
-        if (b->p) (void)hipFree(b->p);
-    for (View &v : c->views)
-        if (v.masks.p) (void)hipFree(v.masks.p);
-    if (c->rows) (void)hipFree(c->rows);
-    pinned_free(c->pin, c->pin_cap);
-    if (c->pin_small) (void)hipHostFree(c->pin_small);
-    if (c->stage) (void)hipHostFree(c->stage);
-    if (c->zc_out) (void)hipHostFree(c->zc_out);
-    if (c->hint_pin) (void)hipHostFree(c->hint_pin);
-    if (c->hint_prior_pin) (void)hipHostFree(c->hint_prior_pin);
-    if (c->order_pin) (void)hipHostFree(c->order_pin);
-    mh_ahead_destroy(c);
-    if (c->mh_pin) (void)hipHostFree(c->mh_pin);
-    for (int p = 0; p < 2; p++)
-        if (c->mh_ev[p]) (void)hipEventDestroy(c->mh_ev[p]);
-    for (int s = 0; s < BNPC_TILE_SLOTS; s++) {
-        pinned_free(c->tile_pin[s], c->tile_cap[s]);
-        pinned_free(c->tile_rows[s], c->tile_rows_cap[s]);
-        pinned_free(c->tile_cells[s], c->tile_cells_cap[s]);
-        pinned_free(c->tile_hint[s], c->tile_hint_cap[s]);
-        pinned_free(c->tile_prior[s], c->tile_prior_cap[s]);
-        if (c->tile_done[s]) (void)hipEventDestroy(c->tile_done[s]);
-    }
-    for (int s = 0; s < 2; s++) {
-        if (c->tile_summed[s]) (void)hipEventDestroy(c->tile_summed[s]);
-        if (c->tile_out_free[s]) (void)hipEventDestroy(c->tile_out_free[s]);
-    }
-    if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
-    if (c->ev_hints) (void)hipEventDestroy(c->ev_hints);
-    if (c->ev0) (void)hipEventDestroy(c->ev0);
-    if (c->ev1) (void)hipEventDestroy(c->ev1);
-    if (c->stream) (void)hipStreamDestroy(c->stream);
-    if (c->side_stream) (void)hipStreamDestroy(c->side_stream);
-    delete c;
-    return 0;
-}
-
-extern "C" int bnpc_reload_options(bnpc_ctx *c)
-{
-    ARGCHK(c, "ctx is NULL");
-    read_tunables(c->tun);
-    return 0;
-}
-
-extern "C" int bnpc_shape(const bnpc_ctx *c, int64_t *N, int64_t *M)
-{
-    ARGCHK(c, "ctx is NULL");
-    if (N) *N = c->N;
-    if (M) *M = c->M;
-    return 0;
-}
-
-// the {ones, zeros} words of one cell's row (bnpc_sweeps.cpp: native births)
-const unsigned long long *bnpc_ctx_row(const bnpc_ctx *c, int64_t cell,
-                                       int64_t *M, int *W)
-{
-    if (!c || cell < 0 || cell >= c->N || c->host_rows.empty()) return nullptr;
-    if (M) *M = c->M;
-    if (W) *W = c->W;
-    return (const unsigned long long *)(c->host_rows.data()
-                                        + (size_t)cell * c->W);
-}
-
-extern "C" int bnpc_cell_counts(bnpc_ctx *c, int32_t *n1, int32_t *n0)
-{
-    ARGCHK(c && n1 && n0, "NULL argument");
-    memcpy(n1, c->cell_n1.data(), c->N * sizeof(int32_t));
-    memcpy(n0, c->cell_n0.data(), c->N * sizeof(int32_t));
-    return 0;
-}
-
-extern "C" int bnpc_view_set(bnpc_ctx *c, int view, const int64_t *cells,
-                             int64_t n)
-{
-    ARGCHK(c, "ctx is NULL");
-    ARGCHK(view >= 1 && view < BNPC_MAX_VIEWS, "view out of range");
-    ARGCHK(n >= 0 && (n == 0 || cells), "cells is NULL");
-    for (int64_t i = 0; i < n; i++)
-        ARGCHK(cells[i] >= 0 && cells[i] < c->N, "cell index out of range");
-    HIPCHK(hipSetDevice(c->device));
-    if (n == 0) {
-        c->views[view].n = 0;
-        c->views[view].nblk = 0;
-        return 0;
-    }
-    // The cell list travels through a pinned buffer of its own (N entries,
-    // read in place by the gather kernel), so the call returns without
-    // waiting for the device: what uses the view is queued behind the gather
-    // on the same stream, and the buffer is only written again once the
-    // gather that read it last has finished (an event; it has, long since,
-    // in a split / merge move: a 12 us wait per move otherwise).
-    if (!c->view_cells_pin) {
-        void *pin = nullptr, *dev = nullptr;
-        if (hipHostMalloc(&pin, (size_t)c->N * sizeof(long long),
-                          hipHostMallocDefault) == hipSuccess
-            && hipHostGetDevicePointer(&dev, pin, 0) == hipSuccess
-            && hipEventCreateWithFlags(&c->view_cells_read,
-                                       hipEventDisableTiming) == hipSuccess) {
-            c->view_cells_pin = pin;
-            c->view_cells_dev = (const long long *)dev;
-        } else {
-            (void)hipGetLastError();
-            if (pin) (void)hipHostFree(pin);
-        }
-    }
-    if (c->view_cells_pin && n <= c->N && !c->any_tile_pending()) {
-        if (c->view_cells_busy) {
-            HIPCHK(hipEventSynchronize(c->view_cells_read));
-            c->view_cells_busy = false;
-        }
-        memcpy(c->view_cells_pin, cells, n * sizeof(long long));
-        if (build_view(c, view, c->view_cells_dev, n)) return 1;
-        HIPCHK(hipEventRecord(c->view_cells_read, c->stream));
-        c->view_cells_busy = true;
-        return 0;
-    }
-    if (arena_reset(c)) return 1;
-    const long long *d_cells = (const long long *)stage_in_place(
-        c, cells, n * sizeof(long long));
-    if (!d_cells) {
-        if (ensure(c->cells, n * sizeof(long long))) return 1;
-        if (h2d(c, c->cells.p, cells, n * sizeof(long long))) return 1;
-        d_cells = (const long long *)c->cells.p;
-    }
-    if (build_view(c, view, d_cells, n)) return 1;
-    // the caller's buffer is only borrowed: finish the copy before returning
-    HIPCHK(hipStreamSynchronize(c->stream));
-    return 0;
-}
-
-static int ensure_host(void **p, size_t *cap, size_t bytes)
-{
-    if (bytes <= *cap) return 0;
-    pinned_free(*p, *cap);
-    *p = nullptr;
-    *cap = 0;
-    // tiles of a sweep are sized to a byte budget: little slack is needed
-    return pinned_alloc(p, cap, bytes + bytes / 16 + 4096);
-}
-
-// bnpc_view_set for a tile of a tiled sweep: the cell list is staged in the
-// tile slot's own pinned buffer (read in place by the gather kernel) and
-// NOTHING is waited for - the stream may hold the sums of the tiles issued
-// before, which a synchronisation here would serialise with the host.  The
-// view is for work issued behind it on the context's stream
-// (bnpc_ll_rows_issue on the same slot).
-extern "C" int bnpc_view_set_slot(bnpc_ctx *c, int view, const int64_t *cells,
-                                  int64_t n, int slot)
-{
-    ARGCHK(c, "ctx is NULL");
-    ARGCHK(view >= 1 && view < BNPC_MAX_VIEWS, "view out of range");
-    ARGCHK(slot >= 0 && slot < BNPC_TILE_SLOTS, "slot out of range");
-    ARGCHK(n > 0 && cells, "empty cell list");
-    ARGCHK(!c->tile_pending[slot], "slot has an unconsumed tile");
-    for (int64_t i = 0; i < n; i++)
-        ARGCHK(cells[i] >= 0 && cells[i] < c->N, "cell index out of range");
-    HIPCHK(hipSetDevice(c->device));
-    if (ensure_lanes(c)) return 1;
-    // (for all N cells at once: tiles grow as the clusters die, and growing
-    // a pinned buffer means hipHostFree - a device-wide synchronisation of
-    // ~5 ms in the middle of the pipeline; measured: 33 of them, 0.17 s of a
-    // config-5 first sweep)
-    if (ensure_host(&c->tile_cells[slot], &c->tile_cells_cap[slot],
-                    std::max<int64_t>(n, c->N) * sizeof(long long)))
-        return 1;
-    memcpy(c->tile_cells[slot], cells, n * sizeof(long long));
-    void *d = nullptr;
-    HIPCHK(hipHostGetDevicePointer(&d, c->tile_cells[slot], 0));
-    // Tiles grow as the clusters die (1024 cells, then 1536, 2048, ...), and
-    // growing a device buffer means hipFree - a device-wide synchronisation
-    // in the middle of the pipeline.  Room for 4 x the first tile, at least
-    // 16384 cells (all cells if there are fewer), is taken at once.
-    View &v = c->views[view];
-    int64_t room = std::max<int64_t>(4 * n, 16384);
-    room = std::min<int64_t>(std::max<int64_t>(room, n), std::max(c->N, n));
-    if (ensure(v.masks, ((size_t)((room + 63) / 64) * c->Mpad + 8)
-                            * sizeof(ulonglong2)))
-        return 1;
-    return build_view(c, view, (const long long *)d, n);
-}
-
-extern "C" int bnpc_view_size(const bnpc_ctx *c, int view, int64_t *n)
-{
-    ARGCHK(c && n, "NULL argument");
-    ARGCHK(view >= 0 && view < BNPC_MAX_VIEWS, "view out of range");
-    *n = c->views[view].n;
     return 0;
 }
 
@@ -3721,6 +2717,16 @@ extern "C" int bnpc_view_counts(bnpc_ctx *c, int view, const int64_t *labels,
     return rc;
 }
 
+// the counts of bnpc_view_counts into c->cnt, `defer` as counts_from_masks
+// (bnpc_rg_counts_and_batch: the batch's screen is queued behind them)
+int view_label_counts(bnpc_ctx *c, int view, const int64_t *labels,
+                      int64_t G, int32_t *n1, int32_t *n0, const int **defer)
+{
+    return counts_from_masks(c, view,
+        [=](int64_t s) -> int64_t { return labels[s]; }, G, c->cnt, n1, n0,
+        defer);
+}
+
 extern "C" int bnpc_colcounts(bnpc_ctx *c, const int64_t *cells,
                               const int64_t *seg_offsets, int64_t G,
                               int32_t *n1, int32_t *n0)
@@ -3748,10 +2754,10 @@ extern "C" int bnpc_colcounts(bnpc_ctx *c, const int64_t *cells,
     return 0;
 }
 
-static int colcounts_by_label_impl(bnpc_ctx *c, const int64_t *assignment,
-                                   const int64_t *ids, int64_t K,
-                                   int32_t *n1, int32_t *n0,
-                                   const int **defer)
+int colcounts_by_label_impl(bnpc_ctx *c, const int64_t *assignment,
+                            const int64_t *ids, int64_t K,
+                            int32_t *n1, int32_t *n0,
+                            const int **defer)
 {
     if (defer) *defer = nullptr;
     ARGCHK(c && assignment && ids, "NULL argument");
@@ -3818,299 +2824,6 @@ extern "C" int bnpc_colcounts_by_label(bnpc_ctx *c, const int64_t *assignment,
 }
 
 
-// ---- device screen of a parameter batch -----------------------------------
-// layout of the pinned block for G x M = E elements (all 16-byte aligned):
-//   U[E] f64 | u[E] f64 | sd_idx[E] i32 | theta[E] f32 | new32[E] f32 |
-//   flags[E] u8
-// (new32: the proposals whose float32 bits the screen vouches for, flag 3)
-struct MHPin {
-    double *U, *u;
-    int32_t *sd_idx;
-    float *theta;
-    float *new32;
-    uint8_t *flags;
-};
-
-static size_t mh_pin_offsets(size_t E, size_t off[6])
-{
-    const size_t Ea = (E + 15) & ~(size_t)15;
-    off[0] = 0;
-    off[1] = off[0] + Ea * 8;
-    off[2] = off[1] + Ea * 8;
-    off[3] = off[2] + Ea * 4;
-    off[4] = off[3] + Ea * 4;
-    off[5] = off[4] + Ea * 4;
-    return off[5] + Ea;
-}
-
-// ---- draws taken AHEAD ------------------------------
-// The draws of a parameter batch - choice(sd, M), M uniforms, M uniforms per
-// cluster, cluster by cluster (libs/CRP.py:328-335) - depend on nothing but
-// the position of the stream, and rank 0's walk through them paces a large
-// batch (0.5 ms of config 5's 0.9 ms parameter phase) while the same thread
-// idles 0.9 ms in front of the sweep's kernel.  So the step posts a WALKER on
-// the aside thread as soon as the stream's way to the batch is known (after a
-// sweep's permutation: one uniform per cell, the alpha test; in a move: after
-// its last variable draw): on a private COPY of the stream it goes that way
-// (`prelude`), notes the state it arrives with (`start`) and draws rows
-// straight into the pinned block, publishing row after row.  The batch adopts
-// them iff the live stream stands exactly at `start` when it begins - any
-// birth, any other draw, any difference makes the two states differ, and the
-// walker's work is dropped (the live stream was never touched).  Same bits
-// by construction: the same generator from the same state.  A batch with
-// more rows than the walker took draws the rest itself, one with fewer
-// continues from the state kept after its last row.
-struct MhAhead {
-    // set by the thread that posts the walker
-    bnpc_mt19937 rng;               // the walker's private stream
-    bnpc_legacy_gauss gauss;
-    std::function<bool(bnpc_mt19937 *, bnpc_legacy_gauss *)> prelude;
-    int64_t rows = 0, M = 0, n_sd = 0;
-    MHPin h;
-    bool active = false;            // posted and not yet taken or dropped
-    // written by the walker
-    std::atomic<int> start_known{0};    // 1: `start` holds; -1: no way known
-    bnpc_mt19937 start;
-    std::atomic<int64_t> rows_ready{0};
-    std::vector<bnpc_mt19937> after_row;
-    std::atomic<int> cancel{0};
-};
-
-static inline void mt_canonical(bnpc_mt19937 &s)
-{
-    if (s.pos >= 624) mt_refill(&s);
-}
-
-static bool mt_same_position(const bnpc_mt19937 &a, const bnpc_mt19937 &b)
-{
-    bnpc_mt19937 x = a, y = b;
-    mt_canonical(x);
-    mt_canonical(y);
-    return x.pos == y.pos && memcmp(x.key, y.key, sizeof x.key) == 0;
-}
-
-// the walker is stopped and forgotten (its draws were not wanted)
-static void mh_ahead_drop(bnpc_ctx *c)
-{
-    MhAhead *ah = c->ahead;
-    if (!ah || !ah->active) return;
-    ah->cancel.store(1, std::memory_order_release);
-    bnpc_aside_wait();
-    ah->active = false;
-}
-
-// A batch of G rows claims a walker's rows: they are kept iff the batch fits
-// them (`fits`: the caller's conditions, then stream, M and n_sd) and the live
-// stream stands exactly where the walker's stood when it began to draw.
-// Returns the number adopted (counted on the context); 0: the walker is
-// dropped.
-static int64_t mh_ahead_claim(bnpc_ctx *c, bool fits, const bnpc_mt19937 *rng,
-                              int64_t G, int64_t M, int64_t n_sd)
-{
-    MhAhead *ah = c->ahead;
-    if (!ah || !ah->active) return 0;
-    bool ok = fits && rng && ah->M == M && ah->n_sd == n_sd
-        && c->tun.mh_ahead != 3;
-    if (ok) {
-        int known = 0;
-        bnpc_spin_until([&] {
-            return (known = ah->start_known.load(std::memory_order_acquire))
-                != 0;
-        });
-        ok = known == 1 && mt_same_position(ah->start, *rng);
-    }
-    if (!ok) {
-        mh_ahead_drop(c);
-        return 0;
-    }
-    const int64_t rows = std::min<int64_t>(ah->rows, G);
-    c->ahead_taken++;
-    c->ahead_rows_taken += rows;
-    return rows;
-}
-
-// returns when the walker has published its rows up to n
-static void mh_ahead_wait_rows(const MhAhead *ah, int64_t n)
-{
-    bnpc_spin_until([&] {
-        return ah->rows_ready.load(std::memory_order_acquire) >= n;
-    });
-}
-
-// A small batch (the rows of a restricted scan) takes a walker's rows whole:
-// the number adopted (the live stream then stands behind them), 0 if there is
-// no walker or the live stream stands elsewhere.
-static int64_t mh_ahead_adopt(bnpc_ctx *c, bnpc_mt19937 *rng, int64_t G,
-                              int64_t M, int64_t n_sd)
-{
-    const int64_t rows = mh_ahead_claim(c, true, rng, G, M, n_sd);
-    if (rows) {
-        mh_ahead_wait_rows(c->ahead, rows);
-        *rng = c->ahead->after_row[(size_t)(rows - 1)];
-        mh_ahead_drop(c);
-    }
-    return rows;
-}
-
-static void mh_ahead_destroy(bnpc_ctx *c)
-{
-    mh_ahead_drop(c);
-    delete c->ahead;
-    c->ahead = nullptr;
-}
-
-static int mh_pin_get(bnpc_ctx *c, size_t E, MHPin &host, MHPin &dev,
-                      bool keep_ahead = false)
-{
-    // (whoever else wants the block ends a walker that writes into it)
-    if (!keep_ahead) mh_ahead_drop(c);
-    size_t off[6];
-    // the block is laid out for its CAPACITY in entries, not for this batch:
-    // rows the walker drew for K + 1 clusters lie where a batch of K finds them
-    size_t need = mh_pin_offsets(E, off);
-    if (E <= c->mh_capE) need = mh_pin_offsets(c->mh_capE, off);
-    if (need > c->mh_cap || E > c->mh_capE) {
-        mh_ahead_drop(c);
-        // the screen of a batch in flight reads this block: nothing is in
-        // flight here (every screened call ends with a synchronisation)
-        if (c->mh_pin) HIPCHK(hipHostFree(c->mh_pin));
-        c->mh_pin = nullptr;
-        c->mh_dev = nullptr;
-        c->mh_cap = 0;
-        // (no head room for the largest blocks: a slice of a batch beyond the
-        // budget never grows)
-        const size_t capE = E + (need < c->tun.mh_pin_max ? E / 4 : 0) + 64;
-        const size_t cap = mh_pin_offsets(capE, off) + 4096;
-        c->mh_capE = 0;
-        const hipError_t e = hipHostMalloc(&c->mh_pin, cap,
-                                           hipHostMallocDefault);
-        if (e == hipErrorOutOfMemory || e == hipErrorMemoryAllocation) {
-            // the caller evaluates the batch without the screen
-            (void)hipGetLastError();
-            c->mh_pin = nullptr;
-            bnpc_set_error("no pinned memory for the screen of a parameter "
-                           "batch (%zu bytes)", cap);
-            return MH_PIN_NO_MEMORY;
-        }
-        HIPCHK(e);
-        void *d = nullptr;
-        HIPCHK(hipHostGetDevicePointer(&d, c->mh_pin, 0));
-        c->mh_dev = (char *)d;
-        c->mh_cap = cap;
-        c->mh_capE = capE;
-    }
-    char *h = (char *)c->mh_pin, *d = c->mh_dev;
-    host = {(double *)(h + off[0]), (double *)(h + off[1]),
-            (int32_t *)(h + off[2]), (float *)(h + off[3]),
-            (float *)(h + off[4]), (uint8_t *)(h + off[5])};
-    dev = {(double *)(d + off[0]), (double *)(d + off[1]),
-           (int32_t *)(d + off[2]), (float *)(d + off[3]),
-           (float *)(d + off[4]), (uint8_t *)(d + off[5])};
-    return 0;
-}
-
-// Post the walker (bnpc_internal.h).  Returns 0 whether or not one was posted
-// (*posted says): no walker is never an error.
-int bnpc_mh_ahead_begin(bnpc_ctx *c, const bnpc_mt19937 *rng,
-                        const bnpc_legacy_gauss *g,
-                        const std::function<bool(bnpc_mt19937 *,
-                                                 bnpc_legacy_gauss *)> &prelude,
-                        int64_t rows, int64_t M, int64_t n_sd, bool *posted,
-                        int64_t min_entries)
-{
-    if (posted) *posted = false;
-    if (!c || !rng || !g || rows < 1 || M != c->M || n_sd < 1 || n_sd > 8)
-        return 0;
-    const int mode = c->tun.mh_ahead;
-    const int64_t E = rows * M;
-    size_t off[6];
-    if (min_entries < 0) min_entries = MH_AHEAD_MIN;
-    if (mode == 0 || !c->tun.mh_screen || rows > MH_AHEAD_MAX_ROWS
-        || E < (mode >= 2 ? MH_SCREEN_MIN : min_entries)
-        || mh_pin_offsets((size_t)E, off) > c->tun.mh_pin_max
-        || c->any_tile_pending())
-        return 0;
-    if (hipSetDevice(c->device) != hipSuccess) {
-        (void)hipGetLastError();
-        return 0;
-    }
-    if (!c->ahead) c->ahead = new MhAhead();
-    MHPin h, d;
-    if (mh_pin_get(c, (size_t)E, h, d)) return 0;   // (drops a walker at work)
-    MhAhead *ah = c->ahead;
-    ah->rng = *rng;
-    ah->gauss = *g;
-    ah->prelude = prelude;
-    ah->rows = rows;
-    ah->M = M;
-    ah->n_sd = n_sd;
-    ah->h = h;
-    ah->start_known.store(0, std::memory_order_relaxed);
-    ah->rows_ready.store(0, std::memory_order_relaxed);
-    ah->cancel.store(0, std::memory_order_relaxed);
-    ah->after_row.resize((size_t)rows);
-    const bool ok = bnpc_aside_start([ah]() {
-        if (ah->prelude && !ah->prelude(&ah->rng, &ah->gauss)) {
-            ah->start_known.store(-1, std::memory_order_release);
-            return;
-        }
-        mt_canonical(ah->rng);
-        ah->start = ah->rng;
-        ah->start_known.store(1, std::memory_order_release);
-        const int64_t M = ah->M;
-        for (int64_t r = 0; r < ah->rows; r++) {
-            if (ah->cancel.load(std::memory_order_acquire)) break;
-            // (non-temporal stores, fenced before the row is published)
-            if (bnpc_mt_mh_draws_to(&ah->rng, 1, M, ah->n_sd,
-                                    ah->h.sd_idx + r * M, ah->h.U + r * M,
-                                    ah->h.u + r * M, true))
-                break;
-            ah->after_row[(size_t)r] = ah->rng;
-            ah->rows_ready.store(r + 1, std::memory_order_release);
-        }
-    });
-    if (!ok) return 0;
-    ah->active = true;
-    c->ahead_begun++;
-    if (posted) *posted = true;
-    return 0;
-}
-
-void bnpc_mh_ahead_drop(bnpc_ctx *c)
-{
-    if (c) mh_ahead_drop(c);
-}
-
-// The rows of a restricted scan's parameter batch (bnpc_rg_counts_and_batch)
-// taken ahead: posted by the scan when its visiting order is drawn - exactly
-// `uniforms` uniforms (one per cell) lie between there and the batch.
-void bnpc_mh_ahead_scan(bnpc_ctx *c, const bnpc_mt19937 *rng, int64_t uniforms,
-                        int64_t rows, int64_t M, int64_t n_sd)
-{
-    static const bnpc_legacy_gauss no_gauss = {};
-    const auto way = [uniforms](bnpc_mt19937 *r, bnpc_legacy_gauss *) {
-        for (int64_t left = 2 * uniforms; left > 0;) {
-            if (r->pos >= 624) mt_refill(r);
-            const int64_t take = std::min<int64_t>(624 - r->pos, left);
-            r->pos += (int32_t)take;
-            left -= take;
-        }
-        return true;
-    };
-    bool posted = false;
-    (void)bnpc_mh_ahead_begin(c, rng, &no_gauss, way, rows, M, n_sd, &posted,
-                              MH_AHEAD_SCAN_MIN);
-}
-
-extern "C" int bnpc_mh_ahead_stats(bnpc_ctx *c, int64_t *begun, int64_t *taken,
-                                   int64_t *rows)
-{
-    ARGCHK(c && begun && taken && rows, "NULL argument");
-    *begun = c->ahead_begun;
-    *taken = c->ahead_taken;
-    *rows = c->ahead_rows_taken;
-    return 0;
-}
 
 // counts of the batch's rows on the device: src 0 = the per-cluster counts of
 // the last bnpc_colcounts_by_label (G rows), src 1 = the two segments of the
@@ -4140,10 +2853,9 @@ static int mh_counts(bnpc_ctx *c, int src, int64_t G, const int **n1,
 }
 
 // rows [g0, g0 + Gp) of the batch
-static int mh_screen_launch(bnpc_ctx *c, int src, const bnpc_mh_args *a,
-                            const MHPin &dev, int64_t g0 = 0, int64_t Gp = -1,
-                            DoneSignal sig = {nullptr, nullptr, 0},
-                            int64_t row0 = 0, int64_t G_all = -1)
+int mh_screen_launch(bnpc_ctx *c, int src, const bnpc_mh_args *a,
+                     const MHPin &dev, int64_t g0, int64_t Gp, DoneSignal sig,
+                     int64_t row0, int64_t G_all)
 {
     const int *n1, *n0;
     int sum_row;
@@ -4169,558 +2881,6 @@ static int mh_screen_launch(bnpc_ctx *c, int src, const bnpc_mh_args *a,
                        (int)a->M, sum_row, k, dev.flags + at,
                        c->tun.screen_theta ? dev.new32 + at : nullptr, sig);
     HIPCHK(hipGetLastError());
-    return 0;
-}
-
-static int mh_screen_argchk(const bnpc_ctx *c, const bnpc_mh_args *a)
-{
-    ARGCHK(c && a, "NULL argument");
-    ARGCHK(a->G > 0 && a->M == c->M, "batch shape does not match the context");
-    ARGCHK(a->old_theta && a->sd && a->n_sd >= 1 && a->n_sd <= 8 && a->sd_idx
-           && a->U && a->u, "NULL argument");
-    ARGCHK(a->FP > 0.0 && a->FP < 1.0 && a->FN > 0.0 && a->FN < 1.0,
-           "error rates must lie in (0, 1)");
-    return 0;
-}
-
-extern "C" int bnpc_mh_screen(bnpc_ctx *c, int counts_src,
-                              const bnpc_mh_args *a, uint8_t *flags,
-                              float *new32)
-{
-    if (int rc = mh_screen_argchk(c, a)) return rc;
-    ARGCHK(flags, "flags is NULL");
-    HIPCHK(hipSetDevice(c->device));
-    const size_t E = (size_t)a->G * a->M;
-    MHPin h, d;
-    if (mh_pin_get(c, E, h, d)) return 1;
-    memcpy(h.U, a->U, E * 8);
-    memcpy(h.u, a->u, E * 8);
-    memcpy(h.sd_idx, a->sd_idx, E * 4);
-    memcpy(h.theta, a->old_theta, E * 4);
-    if (int rc = mh_screen_launch(c, counts_src, a, d)) return rc;
-    HIPCHK(hipStreamSynchronize(c->stream));
-    memcpy(flags, h.flags, E);
-    // (defined where the flag is 3)
-    if (new32) memcpy(new32, h.new32, E * sizeof(float));
-    return 0;
-}
-
-// bnpc_mh_batch with the device screen in front (include/bnpc_hip.h).
-// `pending`: counts the device is still writing into pinned memory behind the
-// stream (n1 rows then n0 rows, a->G x M each): copied into a->n1 / a->n0
-// once the first screen has been waited for - before the host reads any.
-static bool mh_screen_applies(const bnpc_ctx *c, const bnpc_mh_args *a)
-{
-    return !(a->trans_prob || !c->tun.mh_screen || a->screen
-             || a->G * a->M < MH_SCREEN_MIN);
-}
-
-// The counts a fused launch is still writing behind the stream, taken now
-// (a batch that will not wait for its first screen before the host reads them)
-static int mh_take_pending(bnpc_ctx *c, const bnpc_mh_args *a,
-                           const int **pending)
-{
-    if (!*pending) return 0;
-    const size_t E = (size_t)a->G * a->M;
-    HIPCHK(hipStreamSynchronize(c->stream));
-    memcpy((void *)a->n1, *pending, E * sizeof(int32_t));
-    memcpy((void *)a->n0, *pending + E, E * sizeof(int32_t));
-    *pending = nullptr;
-    return 0;
-}
-
-static int mh_batch_dev_impl(bnpc_ctx *c, const bnpc_host_kernels *k,
-                             bnpc_mt19937 *rng, const bnpc_mh_args *a,
-                             int counts_src, int *status, const int *pending,
-                             int64_t row0 = 0, int64_t G_all = -1)
-{
-    ARGCHK(c && a && status, "NULL argument");
-    if (!mh_screen_applies(c, a)) {
-        ARGCHK(!pending, "counts still pending");
-        // (the step's parameter batch without its screen: a walker's draws
-        // are not wanted - the scored batch of a move, counts_src 1, runs
-        // WHILE one walks and leaves it alone)
-        if (counts_src == 0) mh_ahead_drop(c);
-        return bnpc_mh_batch(k, rng, a, status);
-    }
-    if (int rc = mh_screen_argchk(c, a)) return rc;
-    HIPCHK(hipSetDevice(c->device));
-    {
-        // The pinned block has a budget (a first step that is a
-        // move at config 5 brings a batch of K0 x M = 158 M entries - 5.7 GB
-        // pinned per chain without one).  A larger batch is screened in
-        // slices of whole rows that reuse the block: the draws are taken row
-        // by row in the reference's order either way, and nothing of a row
-        // depends on another.
-        size_t off[6];
-        const size_t per_row = mh_pin_offsets((size_t)a->M, off);
-        const int64_t rows_max = std::max<int64_t>(
-            1, (int64_t)(c->tun.mh_pin_max / per_row));
-        if (a->G > rows_max && counts_src == 0 && row0 == 0 && G_all < 0) {
-            if (int rc = mh_take_pending(c, a, &pending)) return rc;
-            *status = 0;
-            for (int64_t g0 = 0; g0 < a->G; g0 += rows_max) {
-                const int64_t Gs = std::min<int64_t>(rows_max, a->G - g0);
-                const size_t at = (size_t)g0 * a->M;
-                bnpc_mh_args b = *a;
-                b.G = Gs;
-                b.old_theta += at;
-                b.n1 += at;
-                b.n0 += at;
-                if (b.known_theta) {
-                    b.known_theta += at;
-                    b.known_prior += at;
-                }
-                b.sd_idx += at;
-                b.U += at;
-                b.u += at;
-                b.new_theta += at;
-                if (b.prior_out) b.prior_out += at;
-                b.A += at;
-                b.log_prob += g0;
-                b.declined += g0;
-                int st = 0;
-                if (int rc = mh_batch_dev_impl(c, k, rng, &b, 0, &st, nullptr,
-                                               g0, a->G))
-                    return rc;
-                // (an element left to SciPy: the caller puts the stream back
-                // and walks the whole batch by the binding - no point in
-                // going on)
-                if (st) {
-                    *status = 1;
-                    return 0;
-                }
-            }
-            return 0;
-        }
-    }
-    static const bool trace = [] {      // BNPC_TIMING=mh
-        const char *e = getenv("BNPC_TIMING");
-        return e && strstr(e, "mh");
-    }();
-    timespec ts0, ts1;
-    if (trace) clock_gettime(CLOCK_MONOTONIC, &ts0);
-    const int64_t G = a->G, M = a->M;
-    const size_t E = (size_t)G * M;
-    MHPin h, d;
-    if (const int prc = mh_pin_get(c, E, h, d, true)) {
-        if (prc != MH_PIN_NO_MEMORY) return 1;
-        // no pinned block: the batch without its screen (the exact arithmetic
-        // of every entry on the team) instead of a failed step
-        if (int rc = mh_take_pending(c, a, &pending)) return rc;
-        return bnpc_mh_batch(k, rng, a, status);
-    }
-    // Parts in a pipeline (batches of 4 rows and more): the draws of part
-    // p + 1 are taken while the device screens part p, and the host evaluates
-    // what a screen left while the next one runs.  Two halves for the batches
-    // of a config-3 step; a LARGE batch (configs 4 and 5: 65 000 - 250 000
-    // entries, 0.2 ms of draws) is cut into up to 8 parts, two of them
-    // issued up front; while the team evaluates what the screen left of part
-    // p, its rank 0 - this thread, the only one that touches the stream -
-    // first takes the draws of part p + 2, stages them and launches their
-    // screen (bnpc_mh_rank0_hook), then joins the evaluation.  (A helper
-    // std::thread did the issuing earlier in round 4: a thread started per
-    // batch on whatever core is free took 80-120 us for the draws of a part
-    // that this thread, warm, takes in 27 - tools/draws_bench.py.)
-    // Draws taken ahead (MhAhead above): adopted iff the live stream stands
-    // where the walker's stood when it began to draw.
-    MhAhead *ah = c->ahead;
-    const int64_t ahead_rows = mh_ahead_claim(
-        c, row0 == 0 && G_all < 0 && counts_src == 0, rng, G, M, a->n_sd);
-    // the walker's part of the batch is over: the live stream continues from
-    // the state kept after the last row taken from it
-    auto ahead_close = [&]() {
-        if (!ahead_rows || !ah->active) return;
-        mh_ahead_wait_rows(ah, ahead_rows);
-        *rng = ah->after_row[(size_t)(ahead_rows - 1)];
-        mh_ahead_drop(c);
-    };
-    const bool threaded = rng && c->tun.done_words && G >= 4 && counts_src == 0
-        && E >= MH_THREADED_MIN;     // "pipelined on rank 0"
-    int parts = (G >= 4 && counts_src == 0) ? 2 : 1;
-    if (threaded)
-        parts = (int)std::max<int64_t>(2, std::min<int64_t>(
-            std::min<int64_t>(8, G), (int64_t)(E / (MH_THREADED_MIN / 2))));
-    int64_t cut[9];
-    for (int p = 0; p <= parts; p++) cut[p] = G * p / parts;
-    // ONE team job for the whole batch (round 6; below): its ranks wait for a
-    // part's verdicts at the first row of it they touch
-    const bool one_job = c->tun.done_words && parts >= 2;
-    for (int p = 0; p < 2; p++)
-        if (!c->mh_ev[p])
-            HIPCHK(hipEventCreateWithFlags(&c->mh_ev[p],
-                                           hipEventDisableTiming));
-    SideLane lane(c);
-    unsigned done_seq[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    double t_draws_us[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    // draws + staging + launch of one part (either thread)
-    auto issue_part = [&](int p) -> int {
-        const int64_t g0 = cut[p], Gp = cut[p + 1] - cut[p];
-        const size_t at = (size_t)g0 * M, n = (size_t)Gp * M;
-        timespec tq0, tq1;
-        if (trace) clock_gettime(CLOCK_MONOTONIC, &tq0);
-        if (rng) {
-            int64_t lo = g0;
-            const int64_t hi = g0 + Gp;
-            if (lo < ahead_rows) {      // rows the walker took (or is taking)
-                const int64_t upto = std::min(hi, ahead_rows);
-                mh_ahead_wait_rows(ah, upto);
-                lo = upto;
-            }
-            if (lo < hi) {              // rows this thread draws
-                ahead_close();
-                const size_t lat = (size_t)lo * M;
-                if (int rc = bnpc_mt_mh_draws_to(rng, hi - lo, M, a->n_sd,
-                                                 h.sd_idx + lat, h.U + lat,
-                                                 h.u + lat, threaded))
-                    return rc;
-            }
-            if (trace) {
-                clock_gettime(CLOCK_MONOTONIC, &tq1);
-                t_draws_us[p] = (tq1.tv_sec - tq0.tv_sec) * 1e6
-                    + (tq1.tv_nsec - tq0.tv_nsec) / 1e3;
-            }
-        } else {
-            memcpy(h.U + at, a->U + at, n * 8);
-            memcpy(h.u + at, a->u + at, n * 8);
-            memcpy(h.sd_idx + at, a->sd_idx + at, n * 4);
-        }
-        memcpy(h.theta + at, a->old_theta + at, n * 4);
-        // (one word for all parts: the launches of a stream finish in order)
-        const DoneSignal sig = make_signal(c, threaded || one_job ? 0 : p,
-                                           &done_seq[p]);
-        if (int rc = mh_screen_launch(c, counts_src, a, d, g0, Gp, sig, row0,
-                                      G_all))
-            return rc;
-        if (!done_seq[p]) HIPCHK(hipEventRecord(c->mh_ev[p & 1], c->stream));
-        return 0;
-    };
-    timespec t_issued[8], t_got[8], t_waited[8], t_hosted[8];
-    // issue one part, keep its time for the trace
-    auto issue_timed = [&](int p) -> int {
-        const int rc = issue_part(p);
-        if (trace) clock_gettime(CLOCK_MONOTONIC, &t_issued[p]);
-        return rc;
-    };
-    int next_issue = 0;
-    {
-        // (parts whose draws are there cost this thread a copy and a launch:
-        // all of them up front)
-        int up_front = threaded ? std::min(2, parts) : parts;
-        while (up_front < parts && ahead_rows >= cut[up_front + 1]
-               && ah->rows_ready.load(std::memory_order_acquire)
-                   >= cut[up_front + 1])
-            up_front++;
-        for (; next_issue < up_front; next_issue++)
-            if (int rc = issue_timed(next_issue)) return rc;
-    }
-    if (trace) clock_gettime(CLOCK_MONOTONIC, &ts1);
-    int64_t kept = 0;
-    double weighted_per_row = 0.0;      // flagged entries of the parts so far
-    *status = 0;
-    bool all_signalled = one_job;
-    for (int p = 0; p < next_issue; p++)
-        all_signalled = all_signalled && done_seq[p] != 0;
-    if (all_signalled) {
-        // ---- the batch as ONE team job ---------------------------------
-        // Round 5 evaluated part after part: a team job per part, its rank 0
-        // issuing the next part but one before it joined - seven wake-ups,
-        // seven barriers and seven tails per config-5 batch, 60-70 us a part
-        // even with the draws taken ahead.  Now the team is started once:
-        // rank 0 (this thread) first issues what is left to issue - a copy
-        // and a launch per part when a walker took the draws, else the draws
-        // too -, copies the counts a fused launch wrote, and joins; every
-        // rank, before it touches a row, waits until the part the row lies
-        // in has been launched and the device's completion word has reached
-        // that launch's number (the parts finish in order on one stream).
-        std::atomic<int> issued(next_issue), ready(0), failed(0);
-        const volatile unsigned *word = c->done_pin;    // slot 0
-        const std::function<bool(int64_t)> gate = [&](int64_t g) -> bool {
-            int p = 0;
-            while (p + 1 < parts && g >= cut[p + 1]) p++;
-            if (ready.load(std::memory_order_acquire) > p) return true;
-            bnpc_spin_until([&] {
-                return failed.load(std::memory_order_relaxed)
-                    || (issued.load(std::memory_order_acquire) > p
-                        && (int)(*word - done_seq[p]) >= 0);
-            }, 4000);
-            if (failed.load(std::memory_order_relaxed)) return false;
-            std::atomic_thread_fence(std::memory_order_acquire);
-            int seen = ready.load(std::memory_order_relaxed);
-            while (seen < p + 1
-                   && !ready.compare_exchange_weak(seen, p + 1,
-                                                   std::memory_order_release))
-            {}
-            return true;
-        };
-        int hook_rc = 0;
-        const int *counts_dev = pending;
-        const std::function<void()> hook = [&]() {
-            while (next_issue < parts && !hook_rc) {
-                hook_rc = issue_timed(next_issue);
-                if (!hook_rc && !done_seq[next_issue]) hook_rc = 1;
-                next_issue++;
-                issued.store(next_issue, std::memory_order_release);
-            }
-            if (hook_rc) {
-                failed.store(1, std::memory_order_relaxed);
-                return;
-            }
-            if (counts_dev) {   // behind the first screen: the counts are there
-                if (!gate(0)) return;
-                memcpy((void *)a->n1, counts_dev, E * sizeof(int32_t));
-                memcpy((void *)a->n0, counts_dev + E, E * sizeof(int32_t));
-            }
-        };
-        bnpc_mh_args b = *a;
-        b.sd_idx = h.sd_idx;
-        b.U = h.U;
-        b.u = h.u;
-        b.screen = h.flags;
-        b.screen_theta = h.new32;
-        if (pending) {          // the evaluation reads them where they are
-            b.n1 = pending;
-            b.n0 = pending + E;
-        }
-        int64_t counts[3] = {0, 0, 0};
-        b.flag_counts = counts;
-        b.flagged_estimate = std::max<int64_t>(
-            1, (int64_t)(c->mh_flagged_share * (double)E));
-        int st = 0;
-        bnpc_mh_rank0_hook(&hook);
-        bnpc_mh_row_gate(&gate);
-        int rc = bnpc_mh_batch(k, nullptr, &b, &st);
-        bnpc_mh_rank0_hook(nullptr);
-        bnpc_mh_row_gate(nullptr);
-        pending = nullptr;
-        if (rc == 0 && hook_rc) {
-            bnpc_set_error("a part of a screened parameter batch could not "
-                           "be issued");
-            rc = hook_rc == 2 ? 2 : 1;
-        }
-        if (rc) {
-            (void)hipStreamSynchronize(c->stream);
-            return rc;
-        }
-        if (st) *status = 1;
-        kept = counts[0] + counts[1] + counts[2];
-        c->mh_flagged_share = ((double)(counts[0] + counts[1])
-            + 0.5 * (double)counts[2]) / (double)E;
-        if (trace)
-            for (int p = 0; p < parts; p++) t_got[p] = t_waited[p] =
-                t_hosted[p] = t_issued[p];
-    } else
-    for (int p = 0; p < parts; p++) {
-        const int64_t g0 = cut[p], Gp = cut[p + 1] - cut[p];
-        const size_t at = (size_t)g0 * M;
-        if (trace) clock_gettime(CLOCK_MONOTONIC, &t_got[p]);
-        if (done_seq[p]) {
-            if (int rc = wait_done(c, threaded || one_job ? 0 : p, done_seq[p]))
-                return rc;
-        } else {
-            HIPCHK(hipEventSynchronize(c->mh_ev[p & 1]));
-        }
-        if (trace) clock_gettime(CLOCK_MONOTONIC, &t_waited[p]);
-        if (pending) {          // the counts were written before the screen
-            memcpy((void *)a->n1, pending, E * sizeof(int32_t));
-            memcpy((void *)a->n0, pending + E, E * sizeof(int32_t));
-            pending = nullptr;
-        }
-        bnpc_mh_args b = *a;
-        b.G = Gp;
-        b.old_theta += at;
-        b.n1 += at;
-        b.n0 += at;
-        if (b.known_theta) {
-            b.known_theta += at;
-            b.known_prior += at;
-        }
-        b.sd_idx = h.sd_idx + at;
-        b.U = h.U + at;
-        b.u = h.u + at;
-        b.new_theta += at;
-        if (b.prior_out) b.prior_out += at;
-        b.A += at;
-        b.log_prob += g0;
-        b.declined += g0;
-        b.screen = h.flags + at;
-        b.screen_theta = h.new32 + at;
-        // (the flags sit in memory the device has just written: a pass over
-        // them - to size the team, to count what was left - is 10-15 us of
-        // misses per part on the calling thread; the team counts while it
-        // works, and the parts of one batch leave about the same share)
-        int64_t counts[3] = {0, 0, 0};
-        b.flag_counts = counts;
-        b.flagged_estimate = p == 0 ? 0
-            : std::max<int64_t>(1, (int64_t)(weighted_per_row * (double)Gp));
-        int st = 0;
-        // rank 0 of this part's evaluation issues the next part but one first
-        int hook_rc = 0;
-        const std::function<void()> hook = [&]() {
-            hook_rc = issue_timed(next_issue++);
-        };
-        if (next_issue < parts) bnpc_mh_rank0_hook(&hook);
-        int rc = bnpc_mh_batch(k, nullptr, &b, &st);
-        bnpc_mh_rank0_hook(nullptr);
-        if (rc == 0) rc = hook_rc;
-        if (rc) {
-            (void)hipStreamSynchronize(c->stream);
-            return rc;
-        }
-        if (st) *status = 1;
-        kept += counts[0] + counts[1] + counts[2];
-        weighted_per_row = ((double)(counts[0] + counts[1])
-            + 0.5 * (double)counts[2]) / (double)Gp;
-        if (trace) clock_gettime(CLOCK_MONOTONIC, &t_hosted[p]);
-    }
-    ahead_close();
-    c->screened += (int64_t)E;
-    c->screen_kept += kept;
-    if (trace) {
-        timespec ts3;
-        clock_gettime(CLOCK_MONOTONIC, &ts3);
-        auto us = [](const timespec &x, const timespec &y) {
-            return (y.tv_sec - x.tv_sec) * 1e6 + (y.tv_nsec - x.tv_nsec) / 1e3;
-        };
-        fprintf(stderr, "[mh_batch_dev] %lld x %lld in %d part(s): draws + "
-                "staging + launches %.1f us, waits + host %.1f us (%lld left)\n",
-                (long long)G, (long long)M, parts, us(ts0, ts1), us(ts1, ts3),
-                (long long)kept);
-        if (threaded)
-            for (int p = 0; p < parts; p++)
-                fprintf(stderr, "[mh_batch_dev]   part %d: issued at %.1f "
-                        "(its draws %.1f), picked up at %.1f, screened at "
-                        "%.1f, evaluated at %.1f us\n", p,
-                        us(ts0, t_issued[p]), t_draws_us[p], us(ts0, t_got[p]),
-                        us(ts0, t_waited[p]), us(ts0, t_hosted[p]));
-    }
-    if (*status != 0) {
-        // the caller's view of the draws (the SciPy-level twin evaluates the
-        // batch from them when the library hands an element back)
-        memcpy(a->sd_idx, h.sd_idx, E * 4);
-        memcpy(a->U, h.U, E * 8);
-        memcpy(a->u, h.u, E * 8);
-    }
-    return 0;
-}
-
-// The second half of a restricted-Gibbs scan (bnpc_rg_scan_step,
-// bnpc_sweeps.cpp) on ONE stream synchronisation: the column counts of the two
-// launch clusters for the new assignment (labels: one per slot of the view),
-// the draws of the parameter batch, its device screen - queued behind the
-// counts it reads - then the counts are copied out and the host evaluates what
-// the screen left.  Scored batches and contexts without the screen take the
-// two calls one after the other.
-int bnpc_rg_counts_and_batch(bnpc_ctx *c, const bnpc_host_kernels *k,
-                             bnpc_mt19937 *rng, int view,
-                             const int64_t *labels, const bnpc_mh_args *a,
-                             int32_t *n1, int32_t *n0, int *status)
-{
-    ARGCHK(c && a && labels && n1 && n0 && status && rng, "NULL argument");
-    const int64_t M = a->M;
-    auto finish_rows = [&]() {
-        if (a->G == 3)
-            for (int64_t m = 0; m < M; m++) {       // the merged cluster
-                n1[2 * M + m] = n1[m] + n1[M + m];
-                n0[2 * M + m] = n0[m] + n0[M + m];
-            }
-    };
-    const bool fused = !a->trans_prob && c->tun.mh_screen
-        && a->G * M >= MH_SCREEN_MIN && !c->any_tile_pending();
-    if (!fused) {
-        if (int rc = bnpc_view_counts(c, view, labels, 2, n1, n0)) return rc;
-        finish_rows();
-        return bnpc_mh_batch_dev(c, k, rng, a, 1, status);
-    }
-    if (int rc = mh_screen_argchk(c, a)) return rc;
-    ARGCHK(view >= 0 && view < BNPC_MAX_VIEWS, "view out of range");
-    HIPCHK(hipSetDevice(c->device));
-    c->cnt_rows = 0;
-    const int *pending = nullptr;
-    if (int rc = counts_from_masks(c, view,
-            [=](int64_t s) -> int64_t { return labels[s]; }, 2, c->cnt, n1, n0,
-            &pending))
-        return rc;
-    c->cnt_rows = 2;
-    const size_t E = (size_t)a->G * M;
-    MHPin h, d;
-    if (mh_pin_get(c, E, h, d, true)) return 1;
-    {
-        // the rows a walker took under the scan's sums and loop (posted when
-        // the scan had drawn its visiting order: one uniform per cell lay
-        // between there and here), the rest by this thread
-        const int64_t got = mh_ahead_adopt(c, rng, a->G, M, a->n_sd);
-        if (got < a->G) {
-            const size_t at = (size_t)got * M;
-            if (int rc = bnpc_mt_mh_draws(rng, a->G - got, M, a->n_sd,
-                                          h.sd_idx + at, h.U + at, h.u + at))
-                return rc;
-        }
-    }
-    memcpy(h.theta, a->old_theta, E * 4);
-    unsigned done_seq = 0;
-    const DoneSignal sig = make_signal(c, 0, &done_seq);
-    if (int rc = mh_screen_launch(c, 1, a, d, 0, -1, sig)) return rc;
-    if (int rc = wait_done(c, 0, done_seq)) return rc;
-    if (pending) {
-        const size_t half = (size_t)2 * M * sizeof(int32_t);
-        memcpy(n1, pending, half);
-        memcpy(n0, pending + (size_t)2 * M, half);
-    }
-    finish_rows();
-    bnpc_mh_args b = *a;
-    b.sd_idx = h.sd_idx;
-    b.U = h.U;
-    b.u = h.u;
-    b.screen = h.flags;
-    b.screen_theta = h.new32;
-    int64_t counts[3] = {0, 0, 0};
-    b.flag_counts = counts;
-    if (int rc = bnpc_mh_batch(k, nullptr, &b, status)) return rc;
-    c->screened += (int64_t)E;
-    c->screen_kept += counts[0] + counts[1] + counts[2];
-    if (*status != 0) {
-        memcpy(a->sd_idx, h.sd_idx, E * 4);
-        memcpy(a->U, h.U, E * 8);
-        memcpy(a->u, h.u, E * 8);
-    }
-    return 0;
-}
-
-extern "C" int bnpc_mh_batch_dev(bnpc_ctx *c, const bnpc_host_kernels *k,
-                                 bnpc_mt19937 *rng, const bnpc_mh_args *a,
-                                 int counts_src, int *status)
-{
-    return mh_batch_dev_impl(c, k, rng, a, counts_src, status, nullptr);
-}
-
-// update_parameters in one call (libs/CRP.py:302-311): the per-cluster
-// column counts for `assignment` (bnpc_colcounts_by_label; they stay resident
-// for bnpc_ll_total) and the screened parameter batch on them, the screens
-// queued behind the counts kernel - the counts reach a->n1 / a->n0 (the
-// caller's arrays, K x M each) with the first screen's results.
-extern "C" int bnpc_label_counts_and_batch(bnpc_ctx *c,
-                                           const bnpc_host_kernels *k,
-                                           bnpc_mt19937 *rng,
-                                           const int64_t *assignment,
-                                           const int64_t *ids,
-                                           const bnpc_mh_args *a, int *status)
-{
-    ARGCHK(c && a && status && a->n1 && a->n0, "NULL argument");
-    const bool fused = mh_screen_applies(c, a) && !c->any_tile_pending();
-    const int *pending = nullptr;
-    if (int rc = colcounts_by_label_impl(c, assignment, ids, a->G,
-            (int32_t *)a->n1, (int32_t *)a->n0, fused ? &pending : nullptr))
-        return rc;
-    return mh_batch_dev_impl(c, k, rng, a, 0, status, pending);
-}
-
-extern "C" int bnpc_mh_screen_stats(bnpc_ctx *c, int64_t *screened,
-                                    int64_t *kept)
-{
-    ARGCHK(c && screened && kept, "NULL argument");
-    *screened = c->screened;
-    *kept = c->screen_kept;
     return 0;
 }
 

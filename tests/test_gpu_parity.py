@@ -1538,7 +1538,7 @@ def test_draws_taken_ahead_change_nothing(mode, kind, pb, knobs, monkeypatch):
     by a walker on the aside thread - on a copy of the stream, under the
     sweep's kernel and loop / under the tail of a move - and adopted by the
     batch iff the live stream stands exactly where the walker's stood
-    (bnpc_mh_ahead_begin, MhAhead in bnpc_kernels.hip).  BNPC_MH_AHEAD=2 takes
+    (bnpc_mh_ahead_begin, MhAhead in bnpc_mhbatch.cpp).  BNPC_MH_AHEAD=2 takes
     them for a batch of ANY size (the default starts at 8192 entries), 3
     takes and then throws them away (the discard path at every step), 0 never
     takes any: after EVERY one of 120 steps the chain is the chain walked
