@@ -1712,6 +1712,8 @@ class Context:
         return np.ctypeslib.as_array(host, shape=(n_rows, ld))
 
     def ll_tables(self, view, L1, L0, out=None):
+        """(slots x K) float64 sums over the caller's tables L1 / L0 (K x M);
+        `out` as in ll_theta (columns K..ld are left untouched)."""
         L1 = np.ascontiguousarray(L1, dtype=np.float64)
         L0 = np.ascontiguousarray(L0, dtype=np.float64)
         if L1.ndim == 1:
@@ -1721,8 +1723,11 @@ class Context:
         n = self.view_size(view)
         if out is None:
             out = np.empty((n, K), dtype=np.float64)
+        assert out.flags['C_CONTIGUOUS'] and out.shape[0] == n \
+            and out.shape[1] >= K and out.dtype == np.float64
         check(self._lib.bnpc_ll_tables(self._h, view, ptr(L1, C.c_double),
-            ptr(L0, C.c_double), K, ptr(out, C.c_double), 0), 'll_tables')
+            ptr(L0, C.c_double), K, ptr(out, C.c_double), out.shape[1]),
+            'll_tables')
         return out
 
     def colcounts(self, segments):

@@ -1257,42 +1257,52 @@ __global__ __launch_bounds__(256) void k_colcounts(
 // Same integers as K3.  No cell lists, no atomics, no zero-fill: thread <->
 // mutation (coalesced 16-byte mask loads), the 4 waves of a workgroup take
 // every 4th block and add up through LDS, 8 segments per thread share each
-// loaded mask.  Results go to a device buffer (kept for K6) and, if given, to
-// pinned host memory in place.
+// loaded mask.  The membership words go through LDS in ranges of `range`
+// blocks (CM_RANGE_MAX at most), so a view of any size is counted; the counts
+// are integers, the grouping of the blocks changes nothing.  Results go to a
+// device buffer (kept for K6) and, if given, to pinned host memory in place.
 // ---------------------------------------------------------------------------
 #define CM_SEG 8
+#define CM_RANGE_MAX 896    // blocks per LDS range: 56 KiB of membership words
 
 __global__ __launch_bounds__(256) void k_counts_masks(
     const ulonglong2 *__restrict__ masks, int Mpad, int M, long long nblk,
     const unsigned long long *__restrict__ member, int G,
     int *__restrict__ n1, int *__restrict__ n0, int *__restrict__ h1,
-    int *__restrict__ h0, DoneSignal done)
+    int *__restrict__ h0, long long range, DoneSignal done)
 {
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int m = blockIdx.x * 64 + lane;
     const int g0 = blockIdx.y * CM_SEG;
-    // The membership words of this workgroup's segments, fetched ONCE with
-    // coalesced loads (they may sit in host memory: a dependent load per
-    // loop iteration would pay the link's latency every time) into LDS,
-    // [blk][CM_SEG]; segments past G read as empty.
     extern __shared__ unsigned long long mem_lds[];
-    for (long long i = threadIdx.x; i < nblk * CM_SEG; i += 256) {
-        const long long b = i / CM_SEG;
-        const int j = (int)(i - b * CM_SEG);
-        mem_lds[i] = (g0 + j < G) ? member[(size_t)(g0 + j) * nblk + b] : 0ull;
-    }
-    __syncthreads();
     int c1[CM_SEG], c0[CM_SEG];
 #pragma unroll
     for (int j = 0; j < CM_SEG; j++) c1[j] = c0[j] = 0;
-    for (long long b = wave; b < nblk; b += 4) {
-        const ulonglong2 mk = masks[(size_t)b * Mpad + m];
-        const unsigned long long *mem = mem_lds + b * CM_SEG;
+    for (long long r0 = 0; r0 < nblk; r0 += range) {
+        const long long nb = nblk - r0 < range ? nblk - r0 : range;
+        // every wave is done with the previous range's words
+        if (r0 > 0) __syncthreads();
+        // The membership words of this workgroup's segments for blocks
+        // r0 .. r0 + nb, fetched ONCE with coalesced loads (they may sit in
+        // host memory: a dependent load per loop iteration would pay the
+        // link's latency every time) into LDS, [blk][CM_SEG]; segments past
+        // G read as empty.
+        for (long long i = threadIdx.x; i < nb * CM_SEG; i += 256) {
+            const long long b = i / CM_SEG;
+            const int j = (int)(i - b * CM_SEG);
+            mem_lds[i] = (g0 + j < G)
+                ? member[(size_t)(g0 + j) * nblk + r0 + b] : 0ull;
+        }
+        __syncthreads();
+        for (long long b = wave; b < nb; b += 4) {
+            const ulonglong2 mk = masks[(size_t)(r0 + b) * Mpad + m];
+            const unsigned long long *mem = mem_lds + b * CM_SEG;
 #pragma unroll
-        for (int j = 0; j < CM_SEG; j++) {
-            c1[j] += __popcll(mk.x & mem[j]);
-            c0[j] += __popcll(mk.y & mem[j]);
+            for (int j = 0; j < CM_SEG; j++) {
+                c1[j] += __popcll(mk.x & mem[j]);
+                c0[j] += __popcll(mk.y & mem[j]);
+            }
         }
     }
     // the membership words are done with: the same LDS takes the partial
@@ -1897,8 +1907,15 @@ static int ll_common(bnpc_ctx *c, int view, int64_t K, int64_t ldo,
                        (size_t)K * sizeof(double));
         }
     } else if (out) {
-        HIPCHK(hipMemcpyAsync(out, c->out.p, out_bytes, hipMemcpyDeviceToHost,
-                              c->stream));
+        // (as above: only columns 0..K of each row)
+        if (ldo == K)
+            HIPCHK(hipMemcpyAsync(out, c->out.p, out_bytes,
+                                  hipMemcpyDeviceToHost, c->stream));
+        else
+            HIPCHK(hipMemcpy2DAsync(out, (size_t)ldo * sizeof(double),
+                                    c->out.p, (size_t)ldo * sizeof(double),
+                                    (size_t)K * sizeof(double), (size_t)v.n,
+                                    hipMemcpyDeviceToHost, c->stream));
         HIPCHK(hipStreamSynchronize(c->stream));
     }
     return 0;
@@ -2657,20 +2674,19 @@ static int counts_from_masks(bnpc_ctx *c, int view, LabelOf label_of,
     int *h1 = zc_host ? (int *)zc_dev : nullptr;
     int *h0 = h1 ? h1 + (size_t)G * c->M : nullptr;
     dim3 grid((unsigned)(c->Mpad / 64), (unsigned)((G + CM_SEG - 1) / CM_SEG));
-    // dynamic LDS: nblk x CM_SEG membership words (50 KB at 50000 cells)
-    size_t lds = (size_t)v.nblk * CM_SEG * sizeof(unsigned long long);
+    // dynamic LDS: range x CM_SEG membership words (50 KB at 50000 cells;
+    // larger views are staged in ranges of CM_RANGE_MAX blocks, 56 KiB)
+    const long long range = std::min<long long>(v.nblk, CM_RANGE_MAX);
+    size_t lds = (size_t)range * CM_SEG * sizeof(unsigned long long);
     const size_t red_bytes = 4 * 2 * CM_SEG * 64 * sizeof(int);
     if (lds < red_bytes) lds = red_bytes;
-    if (lds > 56 * 1024) {
-        bnpc_set_error("view too large for the mask-count kernel");
-        return 1;
-    }
     unsigned done_seq = 0;
     const DoneSignal sig = (zc_host && !defer) ? make_signal(c, 0, &done_seq)
                                                : DoneSignal{nullptr, nullptr, 0};
     BNPC_LAUNCH(k_counts_masks, grid, dim3(256), lds, c->stream,
                        (const ulonglong2 *)v.masks.p, c->Mpad, (int)c->M,
-                       (long long)v.nblk, d_mem, (int)G, d1, d0, h1, h0, sig);
+                       (long long)v.nblk, d_mem, (int)G, d1, d0, h1, h0,
+                       range, sig);
     HIPCHK(hipGetLastError());
     if (zc_host && defer) {
         *defer = zc_host;
@@ -2783,8 +2799,10 @@ int colcounts_by_label_impl(bnpc_ctx *c, const int64_t *assignment,
         offs[pos[a] + 1]++;
     }
     if (K <= c->tun.mask_counts_max
-        && (size_t)c->views[0].nblk * CM_SEG * 8 <= 56 * 1024) {
+        && c->views[0].nblk <= CM_RANGE_MAX) {
         // few clusters: popcounts over the lane masks of the identity view
+        // (a matrix whose membership words take one LDS range; past that the
+        // cell-list kernel)
         const int64_t *pp = pos.data();
         int rc = counts_from_masks(c, 0,
             [=](int64_t s) -> int64_t { return pp[assignment[s]]; }, K,

@@ -52,3 +52,48 @@ void bnpc_oracle_nansum_axis0(const double *v, long r, long c, double *out)
         }
     }
 }
+
+/*
+ * Strict-order sums over per-cluster tables (the arithmetic of the NumPy
+ * table_sums of tests/test_gpu_parity.py: bottleneck.nansum of each row's
+ * elements, in mutation order):
+ *   out[i][k] = sum over m, in order, of T1[m][k] where x[i][m] == 1 and
+ *               T0[m][k] where x[i][m] == 0; other x (missing) are skipped,
+ *               and so are NaN table entries.
+ * x is (n, M) C-contiguous; T1 / T0 are the tables TRANSPOSED to (M, K);
+ * out is (n, K).  Every out[i][k] has its own accumulator that sees the
+ * mutations in order, so the loop over k (innermost, independent entries)
+ * may be vectorised without changing a bit.  Adding +0.0 for a NaN entry is
+ * the same as skipping it: an accumulator that starts at +0.0 never holds
+ * -0.0 (x + (-0.0) == x, and +0.0 + (-0.0) == +0.0).
+ */
+#define TS_ROWS 8
+
+static void table_row_add(double *restrict o, const double *restrict t, long K)
+{
+    for (long k = 0; k < K; k++) {
+        const double a = t[k];
+        o[k] += (a == a) ? a : 0.0;
+    }
+}
+
+void bnpc_oracle_table_sums(const double *x, long n, long M,
+                            const double *T1, const double *T0, long K,
+                            double *out)
+{
+    for (long i = 0; i < n * K; i++) out[i] = 0.0;
+    /* blocks of cells: the table rows of one mutation serve TS_ROWS cells */
+    for (long i0 = 0; i0 < n; i0 += TS_ROWS) {
+        const long i1 = i0 + TS_ROWS < n ? i0 + TS_ROWS : n;
+        for (long m = 0; m < M; m++) {
+            const double *t1 = T1 + (size_t)m * K, *t0 = T0 + (size_t)m * K;
+            for (long i = i0; i < i1; i++) {
+                const double v = x[(size_t)i * M + m];
+                if (v == 1.0)
+                    table_row_add(out + (size_t)i * K, t1, K);
+                else if (v == 0.0)
+                    table_row_add(out + (size_t)i * K, t0, K);
+            }
+        }
+    }
+}

@@ -10,6 +10,7 @@ order the HIP kernel reproduces bit for bit.
 """
 import ctypes
 import os
+from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
@@ -31,6 +32,9 @@ def _load_helper():
         fn = getattr(lib, name)
         fn.restype = None
         fn.argtypes = [_DP, ctypes.c_long, ctypes.c_long, _DP]
+    lib.bnpc_oracle_table_sums.restype = None
+    lib.bnpc_oracle_table_sums.argtypes = [_DP, ctypes.c_long, ctypes.c_long,
+        _DP, _DP, ctypes.c_long, _DP]
     return lib
 
 
@@ -77,3 +81,57 @@ def seqsum(v, axis=None):
 def first_nanargmax(v):
     """bottleneck.nanargmax on a vector: position of the FIRST maximum."""
     return int(np.nanargmax(v))
+
+
+def _table_sums_np(x, L1, L0):
+    """NumPy form of table_sums: one strict-order row sum per cluster."""
+    out = np.empty((x.shape[0], L1.shape[0]))
+    for k in range(L1.shape[0]):
+        el = np.where(x == 1, L1[k], np.where(x == 0, L0[k], np.nan))
+        out[:, k] = seqsum(el, axis=1)
+    return out
+
+
+def _threads():
+    """Row slices run on OMP_NUM_THREADS threads (at most 16; 4 if unset):
+    the machine's CPU count says nothing about this process's share."""
+    try:
+        n = int(os.environ.get('OMP_NUM_THREADS', '4'))
+    except ValueError:
+        n = 4
+    return max(1, min(16, n))
+
+
+def table_sums(data, L1, L0):
+    """out[i, k] = sum over m, in mutation order, NaN skipped, of L1[k, m]
+    where data[i, m] == 1 and L0[k, m] where data[i, m] == 0 (missing cells
+    are skipped): (n, M) data, (K, M) tables -> (n, K) float64."""
+    x = np.ascontiguousarray(data, dtype=np.float64)
+    L1 = np.asarray(L1, dtype=np.float64)
+    L0 = np.asarray(L0, dtype=np.float64)
+    if L1.ndim == 1:
+        L1, L0 = L1[None, :], L0[None, :]
+    n, M = x.shape
+    K = L1.shape[0]
+    assert L1.shape == L0.shape == (K, M)
+    if _LIB is None:
+        return _table_sums_np(x, L1, L0)
+    T1, T0 = np.ascontiguousarray(L1.T), np.ascontiguousarray(L0.T)
+    out = np.empty((n, K))
+    if n == 0 or K == 0:
+        return out
+
+    def rows(r0, r1):     # ctypes releases the GIL for the call
+        _LIB.bnpc_oracle_table_sums(x[r0:].ctypes.data_as(_DP), r1 - r0, M,
+            T1.ctypes.data_as(_DP), T0.ctypes.data_as(_DP), K,
+            out[r0:].ctypes.data_as(_DP))
+
+    threads = _threads()
+    step = max(64, -(-n // (4 * threads)))
+    spans = [(r, min(n, r + step)) for r in range(0, n, step)]
+    if len(spans) == 1:
+        rows(*spans[0])
+    else:
+        with ThreadPoolExecutor(threads) as pool:
+            list(pool.map(lambda s: rows(*s), spans))
+    return out

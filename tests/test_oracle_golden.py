@@ -51,6 +51,59 @@ def test_seqsum_is_sequential():
     assert O.seqsum(np.array([1, 0, 1, -1])) == 1
 
 
+
+def _table_sums_cumsum(x, L1, L0):
+    """Independent form: per cluster the elements, NaN -> 0, a cumulative
+    sum along the mutations (a sequential scan), its last column."""
+    out = np.zeros((x.shape[0], L1.shape[0]))
+    for k in range(L1.shape[0]):
+        el = np.where(x == 1, L1[k], np.where(x == 0, L0[k], np.nan))
+        el = np.where(np.isnan(el), 0.0, el)
+        if el.shape[1]:
+            out[:, k] = np.cumsum(el, axis=1)[:, -1]
+    return out
+
+
+@pytest.mark.parametrize('threads', ['1', '3', '16'])
+def test_table_sums_helper_is_the_strict_order_sum(threads, monkeypatch):
+    """oracle.seqsum.table_sums (the compiled helper, row slices on threads)
+    gives the bits of the NumPy form on ragged shapes, all-missing rows and
+    columns, and tables holding -inf, +0.0, -0.0 and NaN."""
+    from oracle import seqsum as S
+    assert S._LIB is not None, 'oracle/_build/liboracle_seqsum.so not built'
+    monkeypatch.setenv('OMP_NUM_THREADS', threads)
+    rng = np.random.RandomState(int(threads))
+    for n, M, K in ((1, 1, 1), (7, 3, 1), (63, 64, 2), (65, 65, 3),
+            (130, 127, 9), (517, 301, 37), (1000, 17, 130), (9, 0, 4)):
+        x = (rng.random_sample((n, M)) < 0.35).astype(np.float64)
+        x[rng.random_sample(x.shape) < 0.2] = np.nan
+        if n > 2 and M > 2:
+            x[1] = np.nan                   # an all-missing row
+            x[:, M - 2] = np.nan            # an all-missing column
+            x[2] = 1.0
+        L1 = np.log(rng.uniform(size=(K, M)))
+        L0 = np.log(rng.uniform(size=(K, M)))
+        if M > 3:
+            L1[0, 1] = -np.inf
+            L0[K - 1, M - 1] = 0.0
+            L1[K - 1, 0] = -0.0
+            L0[0, 3] = np.nan
+        got = S.table_sums(x, L1, L0)
+        assert got.shape == (n, K)
+        assert np.array_equal(got, S._table_sums_np(x, L1, L0),
+            equal_nan=True), (n, M, K)
+        assert np.array_equal(got, _table_sums_cumsum(x, L1, L0),
+            equal_nan=True), (n, M, K)
+        if n > 2 and M > 2:
+            assert np.all(got[1] == 0.0) and not np.any(np.signbit(got[1]))
+        if M > 3:
+            assert np.all(got[x[:, 1] == 1, 0] == -np.inf)
+    # one-dimensional tables are one cluster
+    x = (rng.random_sample((5, 6)) < .5).astype(np.float64)
+    l1, l0 = np.log(rng.uniform(size=6)), np.log(rng.uniform(size=6))
+    assert np.array_equal(S.table_sums(x, l1, l0),
+        S._table_sums_np(x, l1[None], l0[None]))
+
 def test_calc_ll(G):
     g = G['calc_ll']
     for ci in range(int(g['n_cases'])):
