@@ -36,6 +36,7 @@ MAX_VIEWS = 7
 TILE_SLOTS = 4      # include/bnpc_hip.h: BNPC_TILE_SLOTS
 MAX_TRIALS = 4
 HINT_COLS_MAX = 32767   # columns of a hinted sweep (bnpc_top2 holds them as int16)
+SUPPORT_KC = 128    # include/bnpc_hip.h: BNPC_SUPPORT_KC (clusters per pass)
 
 _i64 = C.c_int64
 # array arguments travel as plain addresses (building a typed ctypes pointer
@@ -301,6 +302,9 @@ SIGNATURES = {
     'bnpc_post_mpear': (C.c_int, [C.c_void_p, C.c_void_p, _i64, _pi64]),
     'bnpc_post_genotypes': (C.c_int, [C.c_void_p, _pi32, _i64, _pf, _i64,
         _i64, _i64, _pd]),
+    'bnpc_post_support': (C.c_int, [C.c_void_p, _pi32, _i64, _pi64]),
+    'bnpc_post_pass_times': (C.c_int, [C.c_void_p, _pi32, _i64, C.c_int,
+        C.POINTER(C.c_float)]),
     'bnpc_post_ward': (C.c_int, [C.c_void_p, _pd]),
     'bnpc_post_ward_stats': (C.c_int, [C.c_void_p, C.POINTER(_i64),
         C.POINTER(_i64)]),
@@ -724,6 +728,32 @@ class Posterior:
             par.shape[1], par.shape[2], int(chunk), ptr(out)),
             'post_genotypes')
         return out
+
+    def support(self, labels, K=None):
+        """differ_to[i][k] = sum of differ over the pairs of cell i with the
+        other cells of cluster k (bnpc_post_support): labels, the cluster of
+        every cell, compact in [0, K), K < 65534 (default: the largest label
+        + 1).  -> int64 (N, K); postproc.cluster_support makes the tables."""
+        lab = np.ascontiguousarray(labels, dtype=np.int32)
+        assert lab.shape == (self.N,)
+        if K is None:
+            K = int(lab.max()) + 1
+        K = int(K)
+        out = np.empty((self.N, max(K, 0)), dtype=np.int64)
+        check(load().bnpc_post_support(self._h, ptr(lab), K, ptr(out)),
+            'post_support')
+        return out
+
+    def pass_times(self, labels, reps=3):
+        """Seconds (device events, the fastest of reps) of one launch each
+        of the passes over all pair counts: (k_differ_sum, k_mpear_sums for
+        the one clustering, k_post_support)."""
+        lab = np.ascontiguousarray(labels, dtype=np.int32)
+        assert lab.shape == (self.N,)
+        ms = (C.c_float * 3)()
+        check(load().bnpc_post_pass_times(self._h, ptr(lab),
+            int(lab.max()) + 1, int(reps), ms), 'post_pass_times')
+        return tuple(x / 1e3 for x in ms)
 
     def close(self):
         if getattr(self, '_h', None):

@@ -1459,3 +1459,284 @@ extern "C" int bnpc_post_genotypes(bnpc_post *p, const int32_t *labels,
         for (int64_t m = 0; m < M; m++) geno[(size_t)k * M + m] /= den[k];
     return 0;
 }
+
+// ---------------------------------------------------------------------------
+// Per-cell cluster support (what the reference shows as the N x N posterior
+// similarity heat map, libs/dpmmIO.py:245-274 of the reference, reduced to
+// tables that mean something at any size): for a clustering `labels`,
+//   differ_to[i][k] = sum over cells j != i with labels[j] == k of differ_ij
+// int64, exact; everything else (support, cluster similarity) is the host's.
+//
+// One workgroup owns a block of 64 cells and produces that block's finished
+// rows: it walks all ceil(N / 64) tiles of its stripe through LDS - right of
+// the diagonal as the row stripe (i in the block, j), left of it as the
+// column stripe (i, j in the block: 256-byte runs per i), the diagonal tile
+// once, mirrored - so that every tile is read twice in total, nothing is
+// added to global memory by two workgroups, and every workgroup has the same
+// work.  The condensed rows start at any 4-byte offset, so the loads are
+// 4 bytes per lane, 256 contiguous bytes per wave.
+//
+// A tile sits in LDS as T[other cell][own cell] (rows padded to 65: the
+// transposing stores of a row-stripe tile are conflict-free too).  Thread =
+// (own cell a, a quarter of the other cells b): it adds T[b][a] into
+// acc[labels[b]][a], a 64-bit accumulator in LDS (own cell fastest: the lanes
+// of a wave hit consecutive addresses, the label is a broadcast).  The four
+// waves may meet on one accumulator, so the add is an LDS atomic - integers:
+// the result does not depend on the order.  The next two tiles' 16 counts
+// per thread each are in flight while the current one is added up.
+//
+// K > BNPC_SUPPORT_KC runs in passes (blockIdx.y) of that many clusters;
+// labels outside the pass are skipped.  The accumulators take what the
+// clustering needs, min(K, KC) * 512 bytes: 4 workgroups per compute unit up
+// to 40 clusters, 1 at 128.
+// ---------------------------------------------------------------------------
+#define PS_KC BNPC_SUPPORT_KC
+#define PS_TILE_WORDS (64 * 65 + 64)    // T[64][65], labels of the other cells
+
+static size_t ps_lds_bytes(int64_t K)
+{
+    return (size_t)std::min<int64_t>(K, PS_KC) * 64 * sizeof(unsigned long long)
+        + PS_TILE_WORDS * sizeof(int);
+}
+
+__global__ __launch_bounds__(256) void k_post_support(
+    const int *__restrict__ differ, long long N,
+    const int *__restrict__ labels,         // padded to 64 * ceil(N / 64): -1
+    int K, long long *__restrict__ out)     // [N][K]
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned long long ps_lds[];
+    const int tid = threadIdx.x;
+    const long long nb = (N + 63) / 64, own = blockIdx.x;
+    const int k0 = (int)blockIdx.y * PS_KC;
+    const int kc = K - k0 < PS_KC ? K - k0 : PS_KC;
+    const int kc_lds = K < PS_KC ? K : PS_KC;
+    unsigned long long *acc = ps_lds;                   // [kc][64]
+    int *T = (int *)(ps_lds + (size_t)kc_lds * 64);     // [64][65]
+    int *lab = T + 64 * 65;                             // [64]
+    for (int e = tid; e < kc * 64; e += 256) acc[e] = 0;
+
+    // element (r, c) of tile t: pair (R0 + r, C0 + c), thread -> c fastest;
+    // left of the diagonal the tile's rows are the other cells.  The index of
+    // pair (i, j) is off(i) + j, off(i) = i (2N - i - 1) / 2 - i - 1: one
+    // 64-bit product per tile, then off(i + 4) = off(i) + 4 (N - i) - 14.
+    // A pair outside the triangle reads element 0 and counts as zero: the
+    // loads are unconditional and stay in flight together.
+    const int c = tid & 63, rq = tid >> 6;
+    auto fetch = [&](long long t, int (&v)[16], int &lv) {
+        const int j = (int)(t < own ? own : t) * 64 + c;
+        int i = (int)(t < own ? t : own) * 64 + rq;
+        long long off = (long long)i * (2 * N - i - 1) / 2 - i - 1;
+        const bool inside = j < N;
+#pragma unroll
+        for (int u = 0; u < 16; u++) {
+            const bool pair = inside && i < j;
+            const int x = differ[pair ? off + j : 0];
+            v[u] = pair ? x : 0;
+            off += 4 * (N - i) - 14;
+            i += 4;
+        }
+        lv = labels[t * 64 + c];
+    };
+    // tile t from its registers into LDS, tile t + 2 into the registers,
+    // tile t added up
+    auto step = [&](long long t, int (&v)[16], int &lv) {
+        __syncthreads();                    // the previous tile is added up
+        if (t < own) {                      // other = r, own = c
+#pragma unroll
+            for (int u = 0; u < 16; u++) T[(u * 4 + rq) * 65 + c] = v[u];
+        } else if (t > own) {               // other = c, own = r
+#pragma unroll
+            for (int u = 0; u < 16; u++) T[c * 65 + u * 4 + rq] = v[u];
+        } else {                            // the diagonal tile, mirrored
+#pragma unroll
+            for (int u = 0; u < 16; u++) {
+                const int r = u * 4 + rq;
+                if (r < c) T[c * 65 + r] = T[r * 65 + c] = v[u];
+                if (r == c) T[r * 65 + r] = 0;
+            }
+        }
+        if (rq == 0) lab[c] = lv;
+        __syncthreads();
+        if (t + 2 < nb) fetch(t + 2, v, lv);
+        // own cell a = c, other cells b = 16 rq .. 16 rq + 15; a tile's count
+        // is at most S, the sums over a stripe need the 64 bits
+#pragma unroll 4
+        for (int bb = 0; bb < 16; bb++) {
+            const int b = rq * 16 + bb;
+            const unsigned k = (unsigned)(lab[b] - k0);
+            if (k < (unsigned)kc)
+                atomicAdd(&acc[k * 64 + c],
+                          (unsigned long long)(unsigned)T[b * 65 + c]);
+        }
+    };
+    // two tiles of 16 counts per thread in flight: a workgroup alone on its
+    // compute unit still covers most of the memory latency
+    int va[16], vb[16], la = -1, lb = -1;
+    fetch(0, va, la);
+    if (nb > 1) fetch(1, vb, lb);
+    for (long long t = 0; t < nb; t += 2) {
+        step(t, va, la);
+        if (t + 1 < nb) step(t + 1, vb, lb);
+    }
+    __syncthreads();
+    for (int e = tid; e < 64 * kc; e += 256) {
+        const int a = e / kc, k = e - a * kc;
+        const long long i = own * 64 + a;
+        if (i < N) out[i * K + k0 + k] = (long long)acc[k * 64 + a];
+    }
+}
+
+// the clustering as the kernel takes it: compact in [0, K), none empty,
+// padded to whole blocks with -1; 0 or the return code
+static int ps_labels(const bnpc_post *p, const int32_t *labels, int64_t K,
+                     std::vector<int> &lab)
+{
+    const int64_t N = p->N;
+    lab.assign((size_t)((N + 63) / 64) * 64, -1);
+    std::vector<int64_t> size(K, 0);
+    for (int64_t i = 0; i < N; i++) {
+        if (labels[i] < 0 || labels[i] >= K) {
+            bnpc_set_error("support: cluster label %d of cell %lld is not in "
+                           "[0, %lld)", labels[i], (long long)i, (long long)K);
+            return 2;
+        }
+        lab[i] = labels[i];
+        size[labels[i]]++;
+    }
+    for (int64_t k = 0; k < K; k++) {
+        if (size[k] == 0) {
+            bnpc_set_error("support: cluster %lld has no cells (labels must "
+                           "be compact)", (long long)k);
+            return 2;
+        }
+    }
+    return 0;
+}
+
+// device copies of the labels and the N x K table; 0, 1 or 5 (the table does
+// not fit the device's free memory: the return code of bnpc_post_ward)
+static int ps_buffers(const bnpc_post *p, const std::vector<int> &lab,
+                      int64_t K, GtBuffers &buf, int **d_lab,
+                      long long **d_out)
+{
+    const int64_t N = p->N;
+    size_t free_b = 0, total_b = 0;
+    PCK(hipMemGetInfo(&free_b, &total_b));
+    const size_t need = (size_t)N * K * sizeof(long long)
+        + lab.size() * sizeof(int) + ((size_t)1 << 20);
+    if (need > free_b) {
+        bnpc_set_error("support: the %lld x %lld table needs %.1f GB, %.1f GB "
+                       "of device memory are free", (long long)N, (long long)K,
+                       need / 1e9, free_b / 1e9);
+        return 5;
+    }
+    hipError_t e = buf.alloc(d_lab, lab.size());
+    if (e == hipSuccess) e = buf.alloc(d_out, (size_t)N * K);
+    if (e == hipErrorOutOfMemory) {
+        (void)hipGetLastError();
+        bnpc_set_error("support: out of device memory (%s)",
+                       hipGetErrorString(e));
+        return 5;
+    }
+    PCK(e);
+    PCK(hipMemcpy(*d_lab, lab.data(), lab.size() * sizeof(int),
+                  hipMemcpyHostToDevice));
+    PCK(hipFuncSetAttribute((const void *)k_post_support,
+                            hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (int)ps_lds_bytes(PS_KC)));
+    return 0;
+}
+
+static void ps_launch(const bnpc_post *p, const int *d_lab, int64_t K,
+                      long long *d_out)
+{
+    const unsigned nb = (unsigned)((p->N + 63) / 64);
+    const unsigned passes = (unsigned)((K + PS_KC - 1) / PS_KC);
+    hipLaunchKernelGGL(k_post_support, dim3(nb, passes), dim3(256),
+                       ps_lds_bytes(K), 0, p->differ, (long long)p->N, d_lab,
+                       (int)K, d_out);
+}
+
+extern "C" int bnpc_post_support(bnpc_post *p, const int32_t *labels,
+                                 int64_t K, int64_t *differ_to)
+{
+    if (!p || !labels || !differ_to || K < 1 || K >= (int64_t)GT_MIXED) {
+        bnpc_set_error("bad argument: support needs labels, 1 <= K < 65534 "
+                       "clusters and the output");
+        return 2;
+    }
+    std::vector<int> lab;
+    if (int rc = ps_labels(p, labels, K, lab)) return rc;
+    PCK(hipSetDevice(p->device));
+    GtBuffers buf;
+    int *d_lab = nullptr;
+    long long *d_out = nullptr;
+    if (int rc = ps_buffers(p, lab, K, buf, &d_lab, &d_out)) return rc;
+    ps_launch(p, d_lab, K, d_out);
+    PCK(hipGetLastError());
+    PCK(hipMemcpy(differ_to, d_out, (size_t)p->N * K * sizeof(long long),
+                  hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// diagnostic (tools/posterior_bench.py): the three passes that read the whole
+// matrix of pair counts, one launch each by device events, the fastest of
+// `reps`: ms[0] k_differ_sum, ms[1] k_mpear_sums for the one clustering,
+// ms[2] k_post_support
+extern "C" int bnpc_post_pass_times(bnpc_post *p, const int32_t *labels,
+                                    int64_t K, int reps, float *ms)
+{
+    if (!p || !labels || !ms || K < 1 || K >= (int64_t)GT_MIXED || reps < 1) {
+        bnpc_set_error("bad argument: pass times need labels, 1 <= K < 65534 "
+                       "clusters, reps >= 1 and the output");
+        return 2;
+    }
+    std::vector<int> lab;
+    if (int rc = ps_labels(p, labels, K, lab)) return rc;
+    const int64_t N = p->N;
+    std::vector<unsigned short> lab16(N);
+    for (int64_t i = 0; i < N; i++) lab16[i] = (unsigned short)labels[i];
+    PCK(hipSetDevice(p->device));
+    GtBuffers buf;
+    int *d_lab = nullptr;
+    long long *d_out = nullptr;
+    unsigned short *d_lab16 = nullptr;
+    if (int rc = ps_buffers(p, lab, K, buf, &d_lab, &d_out)) return rc;
+    PCK(buf.alloc(&d_lab16, N));
+    PCK(hipMemcpy(d_lab16, lab16.data(), N * sizeof(unsigned short),
+                  hipMemcpyHostToDevice));
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    PCK(hipEventCreate(&ev[0]));
+    hipError_t e = hipEventCreate(&ev[1]);
+    const long long pairs = (long long)N * (N - 1) / 2;
+    for (int which = 0; which < 3 && e == hipSuccess; which++) {
+        ms[which] = 0.0f;
+        for (int r = 0; r < reps && e == hipSuccess; r++) {
+            // (the sums of the first two land in scratch nobody reads)
+            e = hipMemsetAsync(p->sums, 0, 2 * sizeof(unsigned long long), 0);
+            if (e == hipSuccess) e = hipEventRecord(ev[0], 0);
+            if (which == 0)
+                hipLaunchKernelGGL(k_differ_sum, dim3(1024), dim3(256), 0, 0,
+                                   p->differ, pairs, p->sums);
+            else if (which == 1)
+                hipLaunchKernelGGL(k_mpear_sums, dim3(1024), dim3(256), 0, 0,
+                                   p->differ, (long long)N, d_lab16, 0, 1, 32,
+                                   p->sums + 1);
+            else
+                ps_launch(p, d_lab, K, d_out);
+            if (e == hipSuccess) e = hipGetLastError();
+            if (e == hipSuccess) e = hipEventRecord(ev[1], 0);
+            if (e == hipSuccess) e = hipEventSynchronize(ev[1]);
+            float t = 0.0f;
+            if (e == hipSuccess) e = hipEventElapsedTime(&t, ev[0], ev[1]);
+            if (r == 0 || t < ms[which]) ms[which] = t;
+        }
+    }
+    (void)hipEventDestroy(ev[0]);
+    if (ev[1]) (void)hipEventDestroy(ev[1]);
+    if (e != hipSuccess) {
+        bnpc_set_error("pass times: %s", hipGetErrorString(e));
+        return 1;
+    }
+    return 0;
+}

@@ -261,6 +261,44 @@ def save_geno(out_dir, chain, est, values, cols, header, names=None):
     return paths
 
 
+def save_support(out_dir, chain, est, tables, assignment, names=None):
+    """The -ps tables of postproc.cluster_support for one (chain, estimator)
+    row.  cell_support_<est>_<chain>.tsv: per cell its name (`names`, the
+    loader's cell names, when there is one per cell, else 0..N-1), its
+    cluster, the support of that cluster, the best other cluster with its
+    support, then the support of every cluster;
+    cluster_similarity_<est>_<chain>.tsv: clusters x clusters.  Cluster ids
+    are the labels of `assignment` (cluster k of the tables is the k-th
+    smallest), values %.4f."""
+    assignment = np.asarray(assignment)
+    ids = np.unique(assignment)
+    cluster_of = np.searchsorted(ids, assignment)
+    support = tables['support']
+    N, K = support.shape
+    index = np.arange(N)
+    if names is not None and np.asarray(names).size == N:
+        index = np.asarray(names)
+    tag = f'{chain:0>2}'
+    head = '\t'.join(str(i) for i in ids.tolist())
+    paths = [os.path.join(out_dir, f'cell_support_{est}_{tag}.tsv'),
+        os.path.join(out_dir, f'cluster_similarity_{est}_{tag}.tsv')]
+    nxt = tables['next_cluster']
+    with open(paths[0], 'w') as f:
+        f.write('cell\tcluster\tsupport\tnext_cluster\tnext_support\t'
+            + head + '\n')
+        for i, name in enumerate(index.tolist()):
+            other = ids[nxt[i]] if nxt[i] >= 0 else -1
+            f.write(f'{name}\t{ids[cluster_of[i]]}\t{tables["own"][i]:.4f}\t'
+                f'{other}\t{tables["next_support"][i]:.4f}\t'
+                + '\t'.join(f'{x:.4f}' for x in support[i].tolist()) + '\n')
+    with open(paths[1], 'w') as f:
+        f.write('\t' + head + '\n')
+        for k, row in enumerate(tables['similarity'].tolist()):
+            f.write(f'{ids[k]}\t' + '\t'.join(f'{x:.4f}' for x in row)
+                + '\n')
+    return paths
+
+
 def save_metric(path, column, rows):
     """V_measure.txt / ARI.txt / hammingDist.txt (dpmmIO.py:514-542): a
     tab-separated `chain  estimator  <column>` table, floats as to_csv

@@ -11,6 +11,10 @@ the pair counts stay there, each candidate is one term of ONE pass over
 them); Ward's linkage and the tree cuts are SciPy on the host.
 The per-cluster genotype averaging that follows is a device pass as well
 (bnpc_post_genotypes; host_genotypes is the host loop it is pinned to).
+The -ps tables (per-cell cluster support, cluster similarity: the data of the
+reference's similarity heat map, dpmmIO.py:245-274, summed per cluster) come
+from one more device pass over the pair counts (bnpc_post_support;
+host_support is the host loop it is pinned to).
 The -tc / -td metrics (V-measure, ARI, Hamming; utils.py:49-72) are
 restated from integer counts at the end; tree helpers are out of scope.
 """
@@ -307,14 +311,17 @@ def mean_hierarchy_assignment(assignments, params_full, dist=None):
     return assign, params[assign].T
 
 
-def _mean_hierarchy(assignments, params_full, dist=None):
-    """(MPEAR clustering, per-cluster mean parameters (clusters, muts))"""
+def _mean_hierarchy(assignments, params_full, dist=None, while_open=None):
+    """(MPEAR clustering, per-cluster mean parameters (clusters, muts));
+    while_open(post, assign) is called before the Posterior is closed."""
     assign, post = _mpear(assignments, dist)
     # the device pass runs on the samples the Posterior holds on the device;
     # a clustering handle without it (a host stand-in for the pair counts)
     # leaves the averaging to the host loop
     device = getattr(post, 'genotypes', None)
     try:
+        if while_open is not None:
+            while_open(post, assign)
         if device is not None and assign is not None \
                 and int(np.max(assign)) < 65534:
             params = device(assign, params_full)
@@ -372,11 +379,20 @@ def concat_chain_results(results):
     return pooled
 
 
-def posterior_estimate(results, data):
+def posterior_estimate(results, data, support=False):
     """`-e posterior` (the default estimator), chains pooled
-    (utils.py:195-244)."""
+    (utils.py:195-244).  support=True: the key 'support' holds the tables of
+    cluster_support for the MPEAR clustering, made from the pair counts of
+    the MPEAR scoring while they are still on the device."""
     res = concat_chain_results(results)
-    assign, params = _mean_hierarchy(res['assignments'], res['params'])
+    tables = {}
+    if support:
+        def while_open(post, assign):
+            tables['support'] = posterior_support(post, assign)
+    else:
+        while_open = None
+    assign, params = _mean_hierarchy(res['assignments'], res['params'],
+        while_open=while_open)
     geno = params[assign].T
     called = geno.T.round()
     FN_geno = (((called == 1) & (data == 0)).sum() + EPSILON) \
@@ -388,7 +404,87 @@ def posterior_estimate(results, data):
         'cluster_genotypes': params, 'cluster_of': assign,
         'FN': (np.mean(res['FN']), np.std(res['FN'])),
         'FP': (np.mean(res['FP']), np.std(res['FP'])),
-        'FN_geno': FN_geno, 'FP_geno': FP_geno}
+        'FN_geno': FN_geno, 'FP_geno': FP_geno, **tables}
+
+
+# ---------------------------------------------------------------------------
+# per-cell cluster support and cluster similarity (-ps): the reference's
+# N x N posterior similarity heat map (dpmmIO.py:245-274, drawn below 300
+# cells only), summed per cluster
+# ---------------------------------------------------------------------------
+def host_support(differ, labels):
+    """differ_to[i][k] = sum over cells j != i with labels[j] == k of
+    differ_ij, int64 (N, K), from the condensed pair counts: row by row, no
+    N x N matrix.  (The per-row sums go through np.bincount's float64
+    weights: integers below (N - 1) * S < 2**53, so they are exact.)"""
+    labels = np.asarray(labels, dtype=np.int64)
+    differ = np.asarray(differ)
+    N = labels.size
+    K = int(labels.max()) + 1
+    out = np.zeros((N, K), dtype=np.int64)
+    at = 0
+    for i in range(N - 1):
+        row = differ[at:at + N - 1 - i].astype(np.int64)    # pairs (i, j > i)
+        at += N - 1 - i
+        out[i] += np.bincount(labels[i + 1:], weights=row, minlength=K) \
+            .astype(np.int64)
+        out[i + 1:, labels[i]] += row
+    return out
+
+
+def posterior_support(post, labels):
+    """cluster_support of a clustering from an open clustering handle: the
+    device pass (Posterior.support) where the handle has one and the labels
+    fit it, else the host loop on the fetched pair counts."""
+    labels = np.asarray(labels)
+    device = getattr(post, 'support', None)
+    if device is not None and int(labels.max()) + 1 < 65534:
+        differ_to = device(labels)
+    else:
+        differ_to = host_support(post.differ(), labels)
+    return cluster_support(differ_to, labels, post.S)
+
+
+def cluster_support(differ_to, labels, S):
+    """The -ps tables of a clustering (labels compact in [0, K)) from
+    differ_to (host_support / Posterior.support) and the number of samples S.
+    With n_k the size of cluster k and m_ik = n_k - [labels[i] == k]:
+      support[i][k]    = 1 - differ_to[i][k] / (S m_ik): the mean posterior
+                         probability that cell i shares a label with a member
+                         of cluster k (1.0 for a singleton's own cluster)
+      own              support of every cell's own cluster
+      next_cluster,    the best other cluster (ties: the smallest index) and
+      next_support     its support; -1 and 0 if there is one cluster only
+      similarity[k][l] = 1 - block[k][l] / (S p_kl), block[k][l] the sum of
+                         differ_to[i][l] over the cells of k, p_kl = n_k n_l,
+                         p_kk = n_k (n_k - 1) (1.0 for a singleton's own)."""
+    differ_to = np.asarray(differ_to, dtype=np.int64)
+    labels = np.asarray(labels, dtype=np.int64)
+    N, K = differ_to.shape
+    cells = np.arange(N)
+    n_k = np.bincount(labels, minlength=K).astype(np.int64)
+    m = np.tile(n_k, (N, 1))
+    m[cells, labels] -= 1
+    support = np.ones((N, K))
+    np.divide(differ_to, S * m, out=support, where=m > 0)
+    np.subtract(1.0, support, out=support, where=m > 0)
+    own = support[cells, labels]
+    if K > 1:
+        others = support.copy()
+        others[cells, labels] = -np.inf
+        next_cluster = np.argmax(others, axis=1).astype(np.int64)
+        next_support = others[cells, next_cluster]
+    else:
+        next_cluster = np.full(N, -1, dtype=np.int64)
+        next_support = np.zeros(N)
+    block = np.zeros((K, K), dtype=np.int64)
+    np.add.at(block, labels, differ_to)
+    pairs = np.outer(n_k, n_k) - np.diag(n_k)
+    similarity = np.ones((K, K))
+    np.divide(block, S * pairs, out=similarity, where=pairs > 0)
+    np.subtract(1.0, similarity, out=similarity, where=pairs > 0)
+    return {'support': support, 'own': own, 'next_cluster': next_cluster,
+        'next_support': next_support, 'similarity': similarity}
 
 
 # ---------------------------------------------------------------------------

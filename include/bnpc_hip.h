@@ -1024,6 +1024,26 @@ int bnpc_post_ward_stats(const bnpc_post *post, int64_t *scans,
 int bnpc_post_genotypes(bnpc_post *post, const int32_t *labels, int64_t K,
                         const float *params, int64_t W, int64_t M,
                         int64_t chunk, double *geno);
+/* Per-cell cluster support: what the reference draws as the N x N posterior
+ * similarity heat map (libs/dpmmIO.py:245-274, below 300 cells only), summed
+ * per cluster so that it means something at any size.  For a clustering
+ * labels (N int32, compact in [0, K), K < 65534),
+ *   differ_to[i][k] = sum over cells j != i with labels[j] == k of differ_ij
+ * (N x K int64 row-major, exact): one pass over the pair counts on the
+ * device, BNPC_SUPPORT_KC clusters per pass.  The support of cell i for
+ * cluster k and the clusters' mean similarity follow on the host
+ * (bnpc_amd.postproc.cluster_support).  Return code 2, and nothing launched,
+ * for labels out of range or an empty cluster; 5 if the table does not fit
+ * the device's free memory. */
+#define BNPC_SUPPORT_KC 128
+int bnpc_post_support(bnpc_post *post, const int32_t *labels, int64_t K,
+                      int64_t *differ_to);
+/* diagnostic: milliseconds (device events, the fastest of reps launches) of
+ * the three passes that read all pair counts - ms[0] the plain sum of
+ * bnpc_post_create, ms[1] bnpc_post_mpear for the one clustering, ms[2]
+ * bnpc_post_support - on the post's own matrix */
+int bnpc_post_pass_times(bnpc_post *post, const int32_t *labels, int64_t K,
+                         int reps, float *ms);
 int bnpc_post_destroy(bnpc_post *post);
 
 #ifdef __cplusplus

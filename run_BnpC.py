@@ -14,7 +14,9 @@ and MAP estimators; per estimator the inferred genotypes
 (genotypes_<est>_<chain>.tsv, and genotypes_cont_<est>_<chain>.tsv when they
 are not all 0/1); with -tc V_measure.txt and ARI.txt, with -td
 hammingDist.txt.  Plots, the similarity PDF and -tr tree colouring are not
-part of this build.
+part of this build; -ps (not a reference flag) writes the similarity PDF's
+data summed per cluster: cell_support_posterior_mean.tsv and
+cluster_similarity_posterior_mean.tsv.
 """
 import argparse
 from datetime import datetime
@@ -112,7 +114,19 @@ FLAGS = [
         'and ARI.txt.')),
     ('output', '-td', '--true_data', dict(type=str, default='',
         help='File with the true (error-free) data: writes hammingDist.txt.')),
+    # not a reference flag: absent from the arguments (and from args.txt)
+    # unless it is given - see Args
+    ('output', '-ps', '--posterior_support', dict(action='store_true',
+        default=argparse.SUPPRESS, help='Write the support of every cell '
+        'for every cluster of the posterior clustering and the clusters\' '
+        'mean posterior similarity (needs -e posterior).')),
 ]
+
+
+class Args(argparse.Namespace):
+    """The parsed arguments: the reference's flags as attributes set by the
+    parser; a flag of this build alone reads as its default until given."""
+    posterior_support = False
 
 
 def build_parser():
@@ -133,7 +147,18 @@ def build_parser():
 
 
 def parse_args(argv=None):
-    return build_parser().parse_args(argv)
+    return build_parser().parse_args(argv, namespace=Args())
+
+
+def check_args(args):
+    """Combinations of flags that cannot run: raises SystemExit with the
+    reason (before any chain starts)."""
+    ests = [args.estimator] if isinstance(args.estimator, str) \
+        else list(args.estimator)
+    if getattr(args, 'posterior_support', False) and 'posterior' not in ests:
+        raise SystemExit('-ps / --posterior_support writes tables of the '
+            'posterior clustering: it needs `posterior` among the estimators '
+            f'(-e), which are: {" ".join(ests)}')
 
 
 def save_outputs(args, results, data, out_dir, names=None):
@@ -149,7 +174,8 @@ def save_outputs(args, results, data, out_dir, names=None):
         if est == 'posterior':
             # the reference's per-chain posterior (-sc) indexes its parameter
             # trace inconsistently (utils.py:228-229); chains are pooled here
-            inf = postproc.posterior_estimate(results, data)
+            inf = postproc.posterior_estimate(results, data,
+                support=getattr(args, 'posterior_support', False))
             rows_a.append(('mean', est,
                 ' '.join(str(i) for i in inf['assignment'])))
             inferred.append(('mean', est, inf))
@@ -187,11 +213,16 @@ def save_outputs(args, results, data, out_dir, names=None):
         for key, val in vars(args).items():
             if key == 'time':
                 val = [f'{t:%Y%m%d_%H:%M:%S}' for t in val]
+            if key == 'posterior_support' and not val:
+                continue        # listed only when it is set
             f.write(f'{key}: {val}\n')
     mut_names = names[1] if names is not None else None
     for chain, est, inf in inferred:
         bio.save_geno(out_dir, chain, est, inf['cluster_genotypes'],
             inf['cluster_of'], inf['assignment'], mut_names)
+        if 'support' in inf:
+            bio.save_support(out_dir, chain, est, inf['support'],
+                inf['assignment'], names[0] if names is not None else None)
     # the metric tables list their rows chain by chain, as the reference
     # does (its per-chain dictionary, dpmmIO.py:524-530); the pooled
     # posterior first
@@ -217,6 +248,7 @@ def main(args):
     from bnpc_amd import postproc
     from libs.MCMC import MCMC
 
+    check_args(args)
     if os.path.getsize(args.input) > (4 << 20):
         # large matrices (no row / column names): the packed bit planes, read
         # from the file next to the input when it is current, else scanned

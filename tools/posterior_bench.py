@@ -9,7 +9,12 @@ pass (bnpc_post_genotypes, trace upload included; its kernels alone:
 rocprofv3 --kernel-trace --stats) and - GENO_HOST=1 - the host loop
 (postproc.host_genotypes).
 GENO_TABLE=<dir>: the genotype table writer (io.save_geno) into that
-directory, files removed afterwards."""
+directory, files removed afterwards.
+SUPPORT=1: right after the pair counts are made, the three passes that read
+all of them - k_differ_sum, one k_mpear_sums pass, the support pass
+(k_post_support) - beside each other on that matrix for the C true clusters,
+by device events (Posterior.pass_times), and Posterior.support as a call
+(table to the host included) checked against the two others; then exit."""
 import os
 import sys
 import time
@@ -41,6 +46,27 @@ print(f'N={N} S={S} C={C}: {N * (N - 1) // 2:.3e} pairs')
 t0 = t_all = time.perf_counter()
 post = _lib.Posterior(a)
 t0 = lap('pair counts on the device (k_codist) + their sum', t0)
+if os.environ.get('SUPPORT') == '1':
+    labels = np.unique(base, return_inverse=True)[1]
+    K = int(labels.max()) + 1
+    read = 4 * post.pairs
+    t_sum, t_mpear, t_sup = post.pass_times(labels, reps=5)
+    print(f'  passes over the {read / 1e9:.2f} GB of pair counts, K={K} '
+        '(device events, fastest of 5):')
+    for name, t, times in (('k_differ_sum', t_sum, 1),
+            ('k_mpear_sums, 1 candidate', t_mpear, 1),
+            ('k_post_support (reads twice)', t_sup, 2)):
+        print(f'    {name:32s} {t * 1e3:9.3f} ms  '
+            f'{times * read / t / 1e9:8.1f} GB/s', flush=True)
+    print(f'    support / differ_sum time: {t_sup / t_sum:.2f}x')
+    t0 = time.perf_counter()
+    differ_to = post.support(labels)
+    t0 = lap('Posterior.support (call, N x K table to the host)', t0)
+    print('  sum == 2 differ_sum:', int(differ_to.sum()) == 2 * post.differ_sum,
+        '; own == 2 mpear sum:', int(differ_to[np.arange(N), labels].sum())
+        == 2 * int(post.mpear_sums(labels[None])[0]))
+    post.close()
+    sys.exit(0)
 tree = post.ward()
 t0 = lap('Ward linkage on the device (k_ward_chain|work) + relabel', t0)
 scans, steps = post.ward_stats()
