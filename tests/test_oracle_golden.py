@@ -383,3 +383,98 @@ def test_config5_first_cells_fixture_is_what_its_maker_describes(golden_dir):
     # existing cluster never raises it
     assert np.all(steps[born] >= 0) and np.all(steps[~born] <= 0)
     assert 0.0 <= float(g['peek']) < 1.0
+
+
+# ------------------------- the extended-precision reference of the flat total
+def _total_forms():
+    import test_total_and_screen_forms as T
+    from oracle import likelihood as L
+    if L.TOTAL_REFERENCE is None:
+        pytest.skip('no arithmetic with a 64-bit significand on this host')
+    return T, L
+
+
+def test_total_reference_is_the_sum_it_says():
+    """total_ll_reference against decimal arithmetic (50 digits) element by
+    element - float32 `1 - theta` taken as an input, the bounds of theta,
+    extreme error rates - and against the oracle's get_ll_full on a matrix."""
+    import decimal
+    T, L = _total_forms()
+    D = decimal.Decimal
+    theta = np.array([[T.TMIN, 0.5, T.TMAX, 0.3, 0.7]], dtype=np.float32)
+    n1 = np.array([[3, 0, 1, 0, 7]], dtype=np.int32)
+    n0 = np.array([[0, 2, 5, 0, 11]], dtype=np.int32)
+    with decimal.localcontext() as dc:
+        dc.prec = 50
+        for fp, fn in T.RATES:
+            want = mag = D(0)
+            for th, c1, c0 in zip(theta[0], n1[0], n0[0]):
+                t, o = D(float(th)), D(float(np.float32(1) - th))
+                term = int(c1) * (t * (1 - D(fn)) + o * D(fp)).ln() \
+                    + int(c0) * (t * D(fn) + o * (1 - D(fp))).ln()
+                want += term
+                mag += abs(term)
+            total, got_mag, mass = L.total_ll_reference(theta, n1, n0, fp, fn)
+            assert mass == 29
+            assert abs(D(float(got_mag)) - mag) < D(2) ** -45 * mag
+            # the total itself carries more than a float64 holds: both halves
+            hi = float(total)
+            lo = float(total - type(total)(hi))
+            assert abs(D(hi) + D(lo) - want) < D(2) ** -58 * mag, (fp, fn)
+            assert L.total_ll_distance(hi, total) <= abs(hi) * 2.0 ** -53
+    # theta without counts is not read
+    other = theta.copy()
+    other[0, 3] = 0.9
+    assert L.total_ll_reference(other, n1, n0, .01, .2)[0] \
+        == L.total_ll_reference(theta, n1, n0, .01, .2)[0]
+    # the oracle's flat total from the matrix itself
+    case = T.total_case(257, 255)
+    x = T.total_data(257)[0]
+    m = O.CRP(x, [-1, -1], [1, 1], FN_error=.2, FP_error=.01)
+    flat = m._calc_ll(x, case.theta[case.assign], True)
+    total, mag, _ = T.total_reference(case, 0)
+    assert T.RATES[0] == (.01, .2)
+    assert abs(flat - float(total)) < 1e-12 * mag
+    # ... and the float64 evaluation in the kernel's grouping on a shape small
+    # enough to write the grouping out: 257 elements = block 0 full, block 1
+    # one element; thread j of block 0 meets thread j + 128, + 64, ...
+    case = T.total_case(257, 1)
+    t = case.theta.astype(np.float64).ravel()
+    o = (1 - case.theta).astype(np.float64).ravel()
+    term = case.n1.ravel() * np.log(t * (1.0 - .2) + o * .01) \
+        + case.n0.ravel() * np.log(t * .2 + o * (1.0 - .01))
+    red = list(term[:256])
+    for s in (128, 64, 32, 16, 8, 4, 2, 1):
+        red = [red[j] + red[j + s] for j in range(s)]
+    assert L.total_ll_kernel_order(case.theta, case.n1, case.n0, .01, .2) \
+        == (0.0 + red[0]) + term[256]
+
+
+def test_total_bound_holds_for_float64_in_the_kernels_order():
+    """The bound of the GPU tests (oracle.likelihood.total_ll_bound, derived
+    from k_ll_total's arithmetic) against a NumPy float64 evaluation in the
+    kernel's grouping, at every shape and rate pair of
+    test_total_and_screen_forms.py: inside it with room to spare.  Observed:
+    |float64 - reference| / bound is at most 0.08 over the 52 cases (the
+    roundings do not all point the same way); a ratio above 0.25 would mean
+    the derivation is wrong, not that the margin is too small."""
+    T, L = _total_forms()
+    worst = 0.0
+    for shape in T.SHAPES:
+        case = T.total_case(*shape)
+        assert case.KM == shape[0] * shape[1]
+        blocks = min(-(-case.KM // 256), 256)
+        assert L.total_ll_chain(case.KM) \
+            == -(-case.KM // 65536) + 8 + blocks
+        for j, (fp, fn) in enumerate(T.RATES):
+            total, mag, mass = T.total_reference(case, j)
+            assert mass == case.n1.sum() + case.n0.sum() and mag > 0
+            emu = L.total_ll_kernel_order(case.theta, case.n1, case.n0,
+                fp, fn)
+            bound = L.total_ll_bound(case.KM, mag, mass)
+            ratio = L.total_ll_distance(emu, total) / bound
+            print(f'[total bound] M {case.M} K {case.K} rates {fp, fn}: '
+                f'{emu!r}, ratio {ratio:.4f}')
+            assert ratio < 0.25, (shape, fp, fn, ratio)
+            worst = max(worst, ratio)
+    print(f'[total bound] worst ratio {worst:.4f}')
