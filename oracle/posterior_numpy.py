@@ -119,3 +119,53 @@ def latents_posterior(results, data):
     return {'a': avg(res['DP_alpha']), 'assignment': assign,
         'genotypes': geno, 'FN': avg(res['FN']), 'FP': avg(res['FP']),
         'FN_geno': FN_geno, 'FP_geno': FP_geno}
+
+
+# ---------------------------------------------------------------------------
+# Direct restatements of the two integer quantities the device keeps, without
+# pdist: a second, independent route to the same numbers (pair counts of any
+# integer labels, negative and extreme ones included; sums as Python ints).
+# ---------------------------------------------------------------------------
+def differ_rows(a):
+    """differ[(i, j)] = samples in which cells i and j carry different labels,
+    i < j, condensed in pdist order, int32 - filled one row i at a time:
+    column i of the samples against the columns after it (an int8 copy where
+    the labels fit: equality is all that is looked at)."""
+    a = np.asarray(a)
+    assert a.ndim == 2 and a.dtype.kind in 'iu'
+    S, N = a.shape
+    if a.size and a.min() >= -128 and a.max() <= 127:
+        a = a.astype(np.int8)
+    out = np.empty(N * (N - 1) // 2, dtype=np.int32)
+    at = 0
+    for i in range(N - 1):
+        n = N - 1 - i
+        np.sum(a[:, i:i + 1] != a[:, i + 1:], axis=0, dtype=np.int32,
+            out=out[at:at + n])
+        at += n
+    return out
+
+
+def same_label_sums(differ, labels):
+    """Per candidate clustering labels[c] (C x N integers): the sum of
+    differ_ij over the pairs i < j that share a label, as int64 - group by
+    group, every group's pairs looked up in the condensed vector, added up as
+    Python integers."""
+    differ = np.asarray(differ)
+    labels = np.asarray(labels)
+    assert labels.ndim == 2
+    N = labels.shape[1]
+    assert differ.size == N * (N - 1) // 2
+    start = [i * (2 * N - i - 1) // 2 - i - 1 for i in range(N)]
+    out = np.empty(labels.shape[0], dtype=np.int64)
+    for c, lab in enumerate(labels):
+        order = np.argsort(lab, kind='stable')
+        edges = np.flatnonzero(np.diff(lab[order])) + 1
+        total = 0
+        for members in np.split(order, edges):  # ascending cells of one label
+            for k in range(members.size - 1):
+                js = members[k + 1:]
+                total += int(differ[start[members[k]] + js]
+                    .sum(dtype=np.int64))
+        out[c] = total
+    return out

@@ -478,3 +478,68 @@ def test_total_bound_holds_for_float64_in_the_kernels_order():
             assert ratio < 0.25, (shape, fp, fn, ratio)
             worst = max(worst, ratio)
     print(f'[total bound] worst ratio {worst:.4f}')
+
+
+# ------------------- the pdist-free references of tests/test_posterior_forms
+def _pdist_counts(a):
+    from scipy.spatial.distance import pdist
+    out = np.zeros(a.shape[1] * (a.shape[1] - 1) // 2, dtype=np.int32)
+    for row in a:
+        out += pdist(np.stack([row, row]).T, 'hamming').astype(np.int32)
+    return out
+
+
+def test_differ_rows_is_the_pdist_accumulation(golden_dir):
+    """oracle.posterior_numpy.differ_rows (row by row, no pdist) against the
+    per-sample pdist accumulation on ragged small shapes, with and without
+    labels that fit an int8, and against the reference's own mean distance
+    of the golden samples."""
+    from oracle import posterior_numpy as Q
+    rng = np.random.RandomState(11)
+    for S, N, lo, hi in ((1, 2, 0, 2), (1, 3, 0, 2), (3, 5, -3, 4),
+            (7, 66, 0, 5), (33, 131, -200, 200), (2, 17, 0, 1)):
+        a = rng.randint(lo, hi, size=(S, N))
+        got = Q.differ_rows(a)
+        assert got.dtype == np.int32 and got.shape == (N * (N - 1) // 2,)
+        assert np.array_equal(got, _pdist_counts(a)), (S, N)
+    g = np.load(os.path.join(golden_dir, 'posterior.npz'))
+    a0 = g['r0_assignments'][int(g['r0_burn_in']):]
+    assert np.array_equal(Q.differ_rows(a0) / a0.shape[0], g['dist0'])
+
+
+def test_same_label_sums_is_the_fake_devices():
+    """oracle.posterior_numpy.same_label_sums (group by group through the
+    condensed index) against FakePosterior.mpear_sums (a pdist mask): random
+    candidates, everything in one cluster (the sum of all counts), all
+    singletons (0), labels at the ends of the device's range."""
+    from fake_device import FakePosterior
+    from oracle import posterior_numpy as Q
+    rng = np.random.RandomState(12)
+    for S, N in ((1, 2), (4, 3), (9, 66), (20, 131)):
+        a = rng.randint(0, 4, size=(S, N))
+        fake = FakePosterior(a)
+        lab = rng.randint(0, rng.randint(1, 9, size=(7, 1)), size=(7, N))
+        lab[0] = 0
+        lab[1] = np.arange(N)
+        lab[2] = np.where(lab[2] == 0, 65533, lab[2])
+        got = Q.same_label_sums(fake.differ(), lab)
+        assert got.dtype == np.int64
+        assert np.array_equal(got, fake.mpear_sums(lab)), (S, N)
+        assert got[0] == fake.differ_sum and got[1] == 0
+    assert Q.same_label_sums(fake.differ(), lab[:0]).shape == (0,)
+
+
+def test_differ_rows_takes_labels_at_the_int32_extremes():
+    """Only equality matters: samples whose labels are drawn from [-64, -1],
+    0, INT32_MIN and INT32_MAX count like a copy relabelled to 0 .. 66."""
+    from oracle import posterior_numpy as Q
+    info = np.iinfo(np.int32)
+    pool = np.concatenate([np.arange(-64, 0), [info.min, info.max, 0]]) \
+        .astype(np.int32)
+    rng = np.random.RandomState(13)
+    pick = rng.randint(0, pool.size, size=(9, 70))
+    a = pool[pick]
+    assert a.dtype == np.int32 and a.min() == info.min and a.max() == info.max
+    want = Q.differ_rows(pick)
+    assert np.array_equal(Q.differ_rows(a), want)
+    assert np.array_equal(want, _pdist_counts(pick))
