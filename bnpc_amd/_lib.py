@@ -37,6 +37,10 @@ TILE_SLOTS = 4      # include/bnpc_hip.h: BNPC_TILE_SLOTS
 MAX_TRIALS = 4
 HINT_COLS_MAX = 32767   # columns of a hinted sweep (bnpc_top2 holds them as int16)
 SUPPORT_KC = 128    # include/bnpc_hip.h: BNPC_SUPPORT_KC (clusters per pass)
+# the most cells whose rank pass (bnpc_post_cell_genotypes) works in LDS:
+# bnpc_codist.hip, 8 ceil(N / 32) + 1040 bytes <= CG_LDS_MAX = 65536
+CELL_RANK_LDS_CELLS = 257984
+CELL_TILE = 8       # bnpc_codist.hip: CG_CELLS (cells per workgroup)
 
 _i64 = C.c_int64
 # array arguments travel as plain addresses (building a typed ctypes pointer
@@ -305,6 +309,10 @@ SIGNATURES = {
     'bnpc_post_support': (C.c_int, [C.c_void_p, _pi32, _i64, _pi64]),
     'bnpc_post_pass_times': (C.c_int, [C.c_void_p, _pi32, _i64, C.c_int,
         C.POINTER(C.c_float)]),
+    'bnpc_post_cell_genotypes': (C.c_int, [C.c_void_p, _pf, _i64, _i64, _i64,
+        _i64, _pd, _pd, C.c_void_p]),
+    'bnpc_post_cell_genotypes_times': (C.c_int, [C.c_void_p, _pf, _i64, _i64,
+        _i64, _i64, C.POINTER(C.c_float)]),
     'bnpc_post_ward': (C.c_int, [C.c_void_p, _pd]),
     'bnpc_post_ward_stats': (C.c_int, [C.c_void_p, C.POINTER(_i64),
         C.POINTER(_i64)]),
@@ -753,6 +761,44 @@ class Posterior:
         ms = (C.c_float * 3)()
         check(load().bnpc_post_pass_times(self._h, ptr(lab),
             int(lab.max()) + 1, int(reps), ms), 'post_pass_times')
+        return tuple(x / 1e3 for x in ms)
+
+    def _trace(self, params):
+        par = np.ascontiguousarray(params, dtype=np.float32)
+        if par.ndim != 3 or par.shape[0] != self.S:
+            raise ValueError(f'the parameter trace must be {self.S} samples '
+                f'x rows x mutations, not {par.shape}')
+        return par
+
+    def cell_genotypes(self, params, chunk=0, slab=0, want=(True, True, True)):
+        """The per-cell sums over the posterior (bnpc_post_cell_genotypes):
+        with v the parameter of cell i's cluster in sample s at mutation m,
+        -> (sum1, sum2, ones), each (N, M): the float64 sums of v and of
+        v * v in sample order and the uint32 count of v > 0.5, the bits of
+        postproc.host_cell_genotypes.  params: the samples x W x M trace
+        (float32 draws; float64 padding converts losslessly); chunk: samples
+        per upload (0: about 512 MB); slab: cells per pass over the trace (0:
+        what the free device memory takes).  want: a table that is not wanted
+        is not fetched and comes back as None."""
+        par = self._trace(params)
+        M = par.shape[2]
+        out = [np.empty((self.N, M), dtype=dt) if w else None
+            for w, dt in zip(want, (np.float64, np.float64, np.uint32))]
+        check(load().bnpc_post_cell_genotypes(self._h, ptr(par), par.shape[1],
+            M, int(chunk), int(slab),
+            *[None if o is None else ptr(o) for o in out]),
+            'post_cell_genotypes')
+        return tuple(out)
+
+    def cell_genotypes_times(self, params, chunk=0, slab=0):
+        """Seconds by device events, summed over one cell_genotypes call that
+        brings no table back: (trace uploads, rank kernel, accumulation
+        kernel)."""
+        par = self._trace(params)
+        ms = (C.c_float * 3)()
+        check(load().bnpc_post_cell_genotypes_times(self._h, ptr(par),
+            par.shape[1], par.shape[2], int(chunk), int(slab), ms),
+            'post_cell_genotypes_times')
         return tuple(x / 1e3 for x in ms)
 
     def close(self):

@@ -12,6 +12,7 @@
 // 4 x 4 block of pair counters in registers.  int32 VALU, LDS-broadcast
 // reads; only tiles on or above the diagonal do any work.
 #include <hip/hip_runtime.h>
+#include <limits.h>
 #include <math.h>
 #include <stdint.h>
 #include <string.h>
@@ -1739,4 +1740,339 @@ extern "C" int bnpc_post_pass_times(bnpc_post *p, const int32_t *labels,
         return 1;
     }
     return 0;
+}
+
+// ---------------------------------------------------------------------------
+// Per-cell posterior genotypes (-pg): the model-averaged parameter of every
+// (cell, mutation).  With r_s(i) the row of cell i's cluster in sample s (the
+// distinct labels of the sample below the cell's: gt_rank) and
+// v = (double)P[s][r_s(i)][m],
+//   sum1[i][m] = sum of v, sum2[i][m] = sum of v * v  (float64, one sample at
+//   a time in increasing s from 0.0), ones[i][m] = samples with v > 0.5.
+// postproc.host_cell_genotypes is the host loop this is pinned to, bit for
+// bit: no atomics on the sums, no tree over the samples.
+//
+// Per chunk of the trace and slab of cells, two launches:
+// k_cg_rank   a workgroup per sample: the presence bitmap of its labels and
+//             the prefix popcounts (gt_scan) in LDS, then rank[s][i] as
+//             uint16 for the slab's cells.  Working set 8 ceil(N / 32) + 1040
+//             bytes; past CG_LDS_MAX a global slice per workgroup, as the
+//             genotype pass does.  (Without a rank table it only counts the
+//             sample's clusters: the argument check.)
+// k_cg_accum  thread = (mutation m, CG_CELLS consecutive cells): the lanes of
+//             a wave run along the mutations (256 contiguous bytes of one
+//             parameter row per load), the cells' ranks are the same for the
+//             whole workgroup (one 16-byte load per sample), and the
+//             3 x CG_CELLS accumulators stay in registers over the chunk -
+//             CG_CELLS independent add chains per thread.  Workgroups that
+//             follow each other share the mutation tile, so a cluster's row
+//             is served from cache to all its cells.  Between chunks the
+//             accumulators live in the slab's tables on the device.
+// ---------------------------------------------------------------------------
+#define CG_CELLS 8
+#define CG_LDS_MAX 65536            // two workgroups per compute unit at least
+
+static long long cg_rank_words(long long N)
+{
+    return 260 + 2 * ((N + 31) / 32);
+}
+
+// samples [s0, s0 + sc) of a; cells [i0, i0 + nc) of each into rank[q][pitch]
+// (q = s - s0), the sample's distinct labels into distinct[q]; either output
+// may be NULL
+__global__ __launch_bounds__(256) void k_cg_rank(
+    const int *__restrict__ a, long long s0, int sc, long long N,
+    long long i0, long long nc, long long pitch,
+    unsigned *gscratch, long long stride,
+    unsigned short *__restrict__ rank, int *__restrict__ distinct)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned gt_lds[];
+    unsigned *area = gscratch ? gscratch + blockIdx.x * stride : gt_lds;
+    const long long nw = (N + 31) / 32;
+    unsigned *part = area;
+    unsigned *bm = area + 260;
+    unsigned *pf = bm + nw;
+    const int tid = threadIdx.x;
+    for (int q = blockIdx.x; q < sc; q += gridDim.x) {
+        const int *row = a + (s0 + q) * N;
+        for (long long w = tid; w < nw; w += 256) bm[w] = 0;
+        __syncthreads();
+        for (long long i = tid; i < N; i += 256) {
+            const int L = row[i];
+            atomicOr(&bm[L >> 5], 1u << (L & 31));
+        }
+        __syncthreads();
+        const unsigned total = gt_scan(bm, pf, nw, part);
+        if (rank) {
+            unsigned short *out = rank + (size_t)q * pitch;
+            for (long long i = tid; i < nc; i += 256)
+                out[i] = (unsigned short)gt_rank(bm, pf, row[i0 + i]);
+        }
+        if (distinct && tid == 0) distinct[q] = (int)total;
+        __syncthreads();                    // the area is reused
+    }
+}
+
+// one chunk of sc samples: P is its [sc][W][M] float32 trace, rank its
+// [sc][pitch] rows (pitch a multiple of CG_CELLS, the padding cells rank 0);
+// the tables are the slab's [nc][M]
+__global__ __launch_bounds__(256) void k_cg_accum(
+    const float *__restrict__ P, int sc, int W, long long M,
+    const unsigned short *__restrict__ rank, long long pitch, long long nc,
+    double *__restrict__ sum1, double *__restrict__ sum2,
+    unsigned *__restrict__ ones)
+{
+    const long long m = (long long)blockIdx.y * 256 + threadIdx.x;
+    if (m >= M) return;
+    const long long c0 = (long long)blockIdx.x * CG_CELLS;
+    double a1[CG_CELLS], a2[CG_CELLS];
+    unsigned n1[CG_CELLS];
+#pragma unroll
+    for (int c = 0; c < CG_CELLS; c++) {
+        const bool in = c0 + c < nc;
+        const size_t at = (size_t)(in ? c0 + c : c0) * M + m;
+        a1[c] = in ? sum1[at] : 0.0;
+        a2[c] = in ? sum2[at] : 0.0;
+        n1[c] = in ? ones[at] : 0u;
+    }
+    const unsigned short *rk = rank + c0;
+    const size_t sample = (size_t)W * M;
+    const float *Ps = P + m;
+#pragma unroll 2
+    for (int q = 0; q < sc; q++) {
+        // the workgroup's CG_CELLS ranks: 16 aligned bytes, the same address
+        // in every lane
+        const uint4 packed = *(const uint4 *)rk;
+        const unsigned r2[4] = {packed.x, packed.y, packed.z, packed.w};
+        float f[CG_CELLS];
+#pragma unroll
+        for (int c = 0; c < CG_CELLS; c++) {
+            const unsigned r = (r2[c >> 1] >> (16 * (c & 1))) & 0xffffu;
+            f[c] = Ps[(size_t)r * M];
+        }
+#pragma unroll
+        for (int c = 0; c < CG_CELLS; c++) {
+            const double v = (double)f[c];
+            a1[c] += v;
+            a2[c] += v * v;     // exact product: FMA or not, the same bits
+            n1[c] += v > 0.5 ? 1u : 0u;
+        }
+        rk += pitch;
+        Ps += sample;
+    }
+#pragma unroll
+    for (int c = 0; c < CG_CELLS; c++) {
+        if (c0 + c < nc) {
+            const size_t at = (size_t)(c0 + c) * M + m;
+            sum1[at] = a1[c];
+            sum2[at] = a2[c];
+            ones[at] = n1[c];
+        }
+    }
+}
+
+namespace {
+struct CgEvents {
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    ~CgEvents()
+    {
+        for (hipEvent_t e : ev)
+            if (e) (void)hipEventDestroy(e);
+    }
+};
+}  // namespace
+
+// ms (NULL, or 3 floats): device-event milliseconds summed over the call -
+// ms[0] the trace uploads, ms[1] k_cg_rank, ms[2] k_cg_accum
+static int cg_run(bnpc_post *p, const float *params, int64_t W, int64_t M,
+                  int64_t chunk, int64_t slab, double *sum1, double *sum2,
+                  uint32_t *ones, float *ms)
+{
+    if (!p || !params || W < 1 || W >= (int64_t)GT_MIXED || M < 1
+        || M > (int64_t)65535 * 256 || chunk < 0 || slab < 0) {
+        bnpc_set_error("bad argument: cell genotypes need a 1 <= W < 65534 x "
+                       "M >= 1 trace, chunk >= 0 and slab >= 0");
+        return 2;
+    }
+    if (!p->assign || !p->labels_in_range) {
+        bnpc_set_error("cell genotypes: the sample labels must lie in "
+                       "[0, N = %lld)", (long long)p->N);
+        return 2;
+    }
+    const int64_t S = p->S, N = p->N;
+    PCK(hipSetDevice(p->device));
+    GtBuffers buf;
+    CgEvents evs;
+    auto oom = [](hipError_t e) {
+        (void)hipGetLastError();
+        bnpc_set_error("cell genotypes: out of device memory (%s)",
+                       hipGetErrorString(e));
+        return 5;
+    };
+#define CGA(expr)                                                            \
+    do {                                                                     \
+        hipError_t a_ = (expr);                                              \
+        if (a_ == hipErrorOutOfMemory) return oom(a_);                       \
+        PCK(a_);                                                             \
+    } while (0)
+
+    // every sample's cluster count against the trace's rows, before anything
+    // is added up
+    GtArea area;
+    int *d_distinct;
+    CGA(buf.alloc(&d_distinct, S));
+    if ((size_t)cg_rank_words(N) * 4 <= CG_LDS_MAX) {
+        area.grid = (unsigned)std::min<int64_t>(S, 65535);
+        area.lds = (size_t)cg_rank_words(N) * 4;
+    } else {
+        area.grid = (unsigned)std::min<int64_t>(S, GT_GLOBAL_WG);
+        area.stride = cg_rank_words(N);
+        CGA(buf.alloc(&area.scratch, (size_t)area.grid * area.stride));
+    }
+    std::vector<int> distinct(S);
+    for (int64_t s0 = 0; s0 < S; s0 += INT_MAX) {
+        const int64_t n = std::min<int64_t>(INT_MAX, S - s0);
+        hipLaunchKernelGGL(k_cg_rank, dim3(area.grid), dim3(256), area.lds, 0,
+                           p->assign, (long long)s0, (int)n, (long long)N, 0LL,
+                           0LL, 0LL, area.scratch, area.stride,
+                           (unsigned short *)nullptr, d_distinct + s0);
+        PCK(hipGetLastError());
+    }
+    PCK(hipMemcpy(distinct.data(), d_distinct, S * sizeof(int),
+                  hipMemcpyDeviceToHost));
+    for (int64_t s = 0; s < S; s++) {
+        if (distinct[s] > W) {
+            bnpc_set_error("cell genotypes: sample %lld has %d clusters, the "
+                           "trace %lld rows", (long long)s, distinct[s],
+                           (long long)W);
+            return 2;
+        }
+    }
+
+    // the chunk of the trace, then as many cells as fit beside it
+    const size_t sample_floats = (size_t)W * M;
+    int64_t sc = chunk;
+    if (sc == 0)
+        sc = std::max<int64_t>(1, (int64_t)(((size_t)512 << 20)
+                                            / (sample_floats * sizeof(float))));
+    sc = std::min<int64_t>(std::min(sc, S), INT_MAX);
+    float *d_P;
+    CGA(buf.alloc(&d_P, (size_t)sc * sample_floats));
+    size_t free_b = 0, total_b = 0;
+    PCK(hipMemGetInfo(&free_b, &total_b));
+    // per cell: the three table rows and its ranks (the pitch rounds up)
+    const size_t per_cell = (size_t)M * 20 + (size_t)sc * 2;
+    const size_t margin = ((size_t)64 << 20) + (size_t)sc * 2 * CG_CELLS;
+    const size_t room = free_b > margin ? (free_b - margin) / per_cell : 0;
+    int64_t nc = slab ? std::min(slab, N)
+                      : (int64_t)std::min<size_t>((size_t)N, room);
+    if (nc < 1 || (size_t)nc > room) {
+        bnpc_set_error("cell genotypes: a slab of %lld cells x %lld mutations "
+                       "needs %.1f GB, %.1f GB of device memory are free",
+                       (long long)std::max<int64_t>(nc, 1), (long long)M,
+                       (double)std::max<int64_t>(nc, 1) * per_cell / 1e9,
+                       free_b / 1e9);
+        return 5;
+    }
+    const int64_t pitch = (nc + CG_CELLS - 1) / CG_CELLS * CG_CELLS;
+    unsigned short *d_rank;
+    double *d_sum1, *d_sum2;
+    unsigned *d_ones;
+    CGA(buf.alloc(&d_rank, (size_t)sc * pitch));
+    CGA(buf.alloc(&d_sum1, (size_t)nc * M));
+    CGA(buf.alloc(&d_sum2, (size_t)nc * M));
+    CGA(buf.alloc(&d_ones, (size_t)nc * M));
+#undef CGA
+    // (the padding cells of a row keep rank 0: a row every trace has)
+    PCK(hipMemset(d_rank, 0, (size_t)sc * pitch * sizeof(unsigned short)));
+    if (ms) {
+        ms[0] = ms[1] = ms[2] = 0.0f;
+        PCK(hipEventCreate(&evs.ev[0]));
+        PCK(hipEventCreate(&evs.ev[1]));
+    }
+    // a lap of the device's clock: begin(), the work, end(its slot of ms)
+    int lap_rc = 0;
+    auto begin = [&]() {
+        if (ms && hipEventRecord(evs.ev[0], 0) != hipSuccess) lap_rc = 1;
+    };
+    auto end = [&](int which) {
+        if (!ms) return;
+        float t = 0.0f;
+        if (hipEventRecord(evs.ev[1], 0) != hipSuccess
+            || hipEventSynchronize(evs.ev[1]) != hipSuccess
+            || hipEventElapsedTime(&t, evs.ev[0], evs.ev[1]) != hipSuccess)
+            lap_rc = 1;
+        ms[which] += t;
+    };
+    for (int64_t i0 = 0; i0 < N; i0 += nc) {
+        const int64_t cells = std::min(nc, N - i0);
+        PCK(hipMemset(d_sum1, 0, (size_t)cells * M * sizeof(double)));
+        PCK(hipMemset(d_sum2, 0, (size_t)cells * M * sizeof(double)));
+        PCK(hipMemset(d_ones, 0, (size_t)cells * M * sizeof(unsigned)));
+        for (int64_t s0 = 0; s0 < S; s0 += sc) {
+            const int64_t n = std::min(sc, S - s0);
+            begin();
+            PCK(hipMemcpy(d_P, params + (size_t)s0 * sample_floats,
+                          (size_t)n * sample_floats * sizeof(float),
+                          hipMemcpyHostToDevice));
+            end(0);
+            begin();
+            hipLaunchKernelGGL(k_cg_rank,
+                               dim3((unsigned)std::min<int64_t>(n, area.grid)),
+                               dim3(256), area.lds, 0, p->assign,
+                               (long long)s0, (int)n, (long long)N,
+                               (long long)i0, (long long)cells,
+                               (long long)pitch, area.scratch, area.stride,
+                               d_rank, (int *)nullptr);
+            PCK(hipGetLastError());
+            end(1);
+            begin();
+            hipLaunchKernelGGL(k_cg_accum,
+                               dim3((unsigned)((cells + CG_CELLS - 1) / CG_CELLS),
+                                    (unsigned)((M + 255) / 256)),
+                               dim3(256), 0, 0, d_P, (int)n, (int)W,
+                               (long long)M, d_rank, (long long)pitch,
+                               (long long)cells, d_sum1, d_sum2, d_ones);
+            PCK(hipGetLastError());
+            end(2);
+        }
+        const size_t at = (size_t)i0 * M, count = (size_t)cells * M;
+        if (sum1)
+            PCK(hipMemcpy(sum1 + at, d_sum1, count * sizeof(double),
+                          hipMemcpyDeviceToHost));
+        if (sum2)
+            PCK(hipMemcpy(sum2 + at, d_sum2, count * sizeof(double),
+                          hipMemcpyDeviceToHost));
+        if (ones)
+            PCK(hipMemcpy(ones + at, d_ones, count * sizeof(unsigned),
+                          hipMemcpyDeviceToHost));
+    }
+    PCK(hipDeviceSynchronize());
+    if (lap_rc) {
+        bnpc_set_error("cell genotypes: the device events failed");
+        return 1;
+    }
+    return 0;
+}
+
+extern "C" int bnpc_post_cell_genotypes(bnpc_post *p, const float *params,
+                                        int64_t W, int64_t M, int64_t chunk,
+                                        int64_t slab, double *sum1,
+                                        double *sum2, uint32_t *ones)
+{
+    return cg_run(p, params, W, M, chunk, slab, sum1, sum2, ones, nullptr);
+}
+
+// diagnostic (tools/posterior_bench.py): one bnpc_post_cell_genotypes call
+// without its tables' way back, by device events (see cg_run)
+extern "C" int bnpc_post_cell_genotypes_times(bnpc_post *p,
+                                              const float *params, int64_t W,
+                                              int64_t M, int64_t chunk,
+                                              int64_t slab, float *ms)
+{
+    if (!ms) {
+        bnpc_set_error("bad argument: NULL");
+        return 2;
+    }
+    return cg_run(p, params, W, M, chunk, slab, nullptr, nullptr, nullptr, ms);
 }

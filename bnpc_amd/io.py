@@ -299,6 +299,33 @@ def save_support(out_dir, chain, est, tables, assignment, names=None):
     return paths
 
 
+def save_cell_geno(out_dir, chain, est, tables, names=None):
+    """The -pg tables of postproc.cell_genotypes for one (chain, estimator)
+    row, each mutations x cells, values %.4f:
+    genotypes_cell_prob_<est>_<chain>.tsv the share of the samples in which
+    the cell's parameter rounds to 1, genotypes_cell_cont_<est>_<chain>.tsv
+    its posterior mean, genotypes_cell_sd_<est>_<chain>.tsv its posterior
+    standard deviation.  names: the loader's (cell, mutation) names - columns
+    and rows are named by them where there is one per cell / mutation, else
+    0..N-1 / 0..M-1."""
+    N, M = tables['mean'].shape
+    cells, muts = np.arange(N), np.arange(M)
+    if names is not None and np.asarray(names[0]).size == N:
+        cells = np.asarray(names[0])
+    if names is not None and np.asarray(names[1]).size == M:
+        muts = np.asarray(names[1])
+    index = np.array([str(x) for x in muts.tolist()], dtype=object)
+    tag = f'{chain:0>2}'
+    paths = []
+    for kind, key in (('prob', 'prob'), ('cont', 'mean'), ('sd', 'sd')):
+        path = os.path.join(out_dir, f'genotypes_cell_{kind}_{est}_{tag}.tsv')
+        entries = np.char.mod('%.4f', np.asarray(tables[key]).T)
+        _write_rows(path, cells.tolist(), np.concatenate([index[:, None],
+            entries.astype(object)], axis=1), np.arange(N))
+        paths.append(path)
+    return paths
+
+
 def save_metric(path, column, rows):
     """V_measure.txt / ARI.txt / hammingDist.txt (dpmmIO.py:514-542): a
     tab-separated `chain  estimator  <column>` table, floats as to_csv

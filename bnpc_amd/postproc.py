@@ -15,6 +15,11 @@ The -ps tables (per-cell cluster support, cluster similarity: the data of the
 reference's similarity heat map, dpmmIO.py:245-274, summed per cluster) come
 from one more device pass over the pair counts (bnpc_post_support;
 host_support is the host loop it is pinned to).
+The -pg tables (per-cell posterior genotypes: the parameter of whichever
+cluster a cell was in, averaged over the samples - not a reference output)
+are a device pass over the samples and the parameter trace
+(bnpc_post_cell_genotypes; host_cell_genotypes is the host loop it is pinned
+to).
 The -tc / -td metrics (V-measure, ARI, Hamming; utils.py:49-72) are
 restated from integer counts at the end; tree helpers are out of scope.
 """
@@ -379,16 +384,22 @@ def concat_chain_results(results):
     return pooled
 
 
-def posterior_estimate(results, data, support=False):
+def posterior_estimate(results, data, support=False, cells=False):
     """`-e posterior` (the default estimator), chains pooled
     (utils.py:195-244).  support=True: the key 'support' holds the tables of
     cluster_support for the MPEAR clustering, made from the pair counts of
-    the MPEAR scoring while they are still on the device."""
+    the MPEAR scoring while they are still on the device.  cells=True: the
+    key 'cell_genotypes' holds the tables of cell_genotypes, made from the
+    samples the same handle keeps on the device."""
     res = concat_chain_results(results)
     tables = {}
-    if support:
+    if support or cells:
         def while_open(post, assign):
-            tables['support'] = posterior_support(post, assign)
+            if support:
+                tables['support'] = posterior_support(post, assign)
+            if cells:
+                tables['cell_genotypes'] = cell_genotypes(post,
+                    res['assignments'], res['params'])
     else:
         while_open = None
     assign, params = _mean_hierarchy(res['assignments'], res['params'],
@@ -485,6 +496,53 @@ def cluster_support(differ_to, labels, S):
     np.subtract(1.0, similarity, out=similarity, where=pairs > 0)
     return {'support': support, 'own': own, 'next_cluster': next_cluster,
         'next_support': next_support, 'similarity': similarity}
+
+
+# ---------------------------------------------------------------------------
+# per-cell posterior genotypes (-pg): what the model says about one cell and
+# one mutation, averaged over the posterior samples - independent of the
+# MPEAR cut; not a reference output, so the summation order below is the
+# specification
+# ---------------------------------------------------------------------------
+def host_cell_genotypes(assignments, params_full):
+    """(sum1, sum2, ones), each (cells, muts): with v the float32 parameter
+    params_full[s][r][m] of the row r of cell i's cluster in sample s (r: the
+    distinct labels of the sample below the cell's - any integer labels), as
+    float64, the sums of v and of v * v over the samples, one sample at a
+    time in increasing s from 0.0, and the uint32 count of the samples with
+    v > 0.5 (np.round(v) == 1: half-to-even sends 0.5 to 0).  The plain loop
+    bnpc_post_cell_genotypes is pinned to."""
+    assignments = np.asarray(assignments)
+    S, N = assignments.shape
+    M = params_full.shape[2]
+    sum1 = np.zeros((N, M))
+    sum2 = np.zeros((N, M))
+    ones = np.zeros((N, M), dtype=np.uint32)
+    for s in range(S):
+        rank = np.unique(assignments[s], return_inverse=True)[1].ravel()
+        v = np.asarray(params_full[s], dtype=np.float32)[rank] \
+            .astype(np.float64)
+        sum1 += v
+        sum2 += v * v
+        ones += v > 0.5
+    return sum1, sum2, ones
+
+
+def cell_genotypes(post, assignments, params_full):
+    """The -pg tables, each (cells, muts) float64: 'mean' and 'sd' of the
+    parameter of the cell's cluster over the posterior samples, 'prob' the
+    share of the samples in which it rounds to 1.  From an open clustering
+    handle: the device pass (Posterior.cell_genotypes) where the handle has
+    one, else the host loop; the same arithmetic on the sums either way."""
+    device = getattr(post, 'cell_genotypes', None)
+    if device is not None:
+        sum1, sum2, ones = device(params_full)
+    else:
+        sum1, sum2, ones = host_cell_genotypes(assignments, params_full)
+    S = np.asarray(assignments).shape[0]
+    mean = sum1 / S
+    sd = np.sqrt(np.maximum(sum2 / S - mean * mean, 0))
+    return {'mean': mean, 'sd': sd, 'prob': ones / S}
 
 
 # ---------------------------------------------------------------------------

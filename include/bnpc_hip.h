@@ -1044,6 +1044,33 @@ int bnpc_post_support(bnpc_post *post, const int32_t *labels, int64_t K,
  * bnpc_post_support - on the post's own matrix */
 int bnpc_post_pass_times(bnpc_post *post, const int32_t *labels, int64_t K,
                          int reps, float *ms);
+/* Per-cell posterior genotypes (-pg; not a reference output): the parameter
+ * of whichever cluster a cell was in, sample by sample, summed over the
+ * posterior.  With r_s(i) the row of cell i's cluster in sample s (the
+ * distinct labels of sample s below the cell's own) and
+ * v = (double)params[s][r_s(i)][m], the three N x M tables are
+ *   sum1[i][m]  float64 sum of v, one sample at a time in increasing s from 0
+ *   sum2[i][m]  float64 sum of v * v, in the same order
+ *   ones[i][m]  uint32 count of the samples with v > 0.5
+ * bit for bit what bnpc_amd.postproc.host_cell_genotypes computes; mean, sd
+ * and the probability of a 1 follow on the host (postproc.cell_genotypes).
+ * The post's samples must lie in [0, N); params: the S x W x M float32 trace
+ * on the host, W < 65534, streamed `chunk` samples at a time (0: about 512 MB
+ * per chunk, as bnpc_post_genotypes); slab: the cells whose tables are on the
+ * device at a time (0: as many as the free device memory takes beside the
+ * chunk) - every slab streams the trace again.  Any of the three outputs may
+ * be NULL.  Return code 2, and nothing added up, for sample labels out of
+ * range or a sample with more clusters than the trace has rows; 5 if a slab
+ * does not fit the device's free memory. */
+int bnpc_post_cell_genotypes(bnpc_post *post, const float *params, int64_t W,
+                             int64_t M, int64_t chunk, int64_t slab,
+                             double *sum1, double *sum2, uint32_t *ones);
+/* diagnostic: one bnpc_post_cell_genotypes call without its tables' way back,
+ * milliseconds by device events summed over the call - ms[0] the trace
+ * uploads, ms[1] the rank kernel, ms[2] the accumulation kernel */
+int bnpc_post_cell_genotypes_times(bnpc_post *post, const float *params,
+                                   int64_t W, int64_t M, int64_t chunk,
+                                   int64_t slab, float *ms);
 int bnpc_post_destroy(bnpc_post *post);
 
 #ifdef __cplusplus

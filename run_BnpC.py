@@ -16,7 +16,10 @@ are not all 0/1); with -tc V_measure.txt and ARI.txt, with -td
 hammingDist.txt.  Plots, the similarity PDF and -tr tree colouring are not
 part of this build; -ps (not a reference flag) writes the similarity PDF's
 data summed per cluster: cell_support_posterior_mean.tsv and
-cluster_similarity_posterior_mean.tsv.
+cluster_similarity_posterior_mean.tsv; -pg (not a reference flag either)
+writes the per-cell posterior genotypes, averaged over the samples instead of
+taken from the cell's MPEAR cluster: genotypes_cell_prob_posterior_mean.tsv,
+genotypes_cell_cont_posterior_mean.tsv, genotypes_cell_sd_posterior_mean.tsv.
 """
 import argparse
 from datetime import datetime
@@ -120,6 +123,13 @@ FLAGS = [
         default=argparse.SUPPRESS, help='Write the support of every cell '
         'for every cluster of the posterior clustering and the clusters\' '
         'mean posterior similarity (needs -e posterior).')),
+    ('output', '-pg', '--posterior_genotypes', dict(action='store_true',
+        default=argparse.SUPPRESS, help='Write the genotype of every cell '
+        'averaged over the posterior samples - the probability of a 1, the '
+        'mean and the standard deviation of its cluster\'s parameter - '
+        'instead of the genotype of its cluster (needs -e posterior; one '
+        'more pass over samples x cells x mutations on the GPU: minutes at '
+        '50 000 cells x 5000 mutations).')),
 ]
 
 
@@ -127,6 +137,7 @@ class Args(argparse.Namespace):
     """The parsed arguments: the reference's flags as attributes set by the
     parser; a flag of this build alone reads as its default until given."""
     posterior_support = False
+    posterior_genotypes = False
 
 
 def build_parser():
@@ -159,6 +170,11 @@ def check_args(args):
         raise SystemExit('-ps / --posterior_support writes tables of the '
             'posterior clustering: it needs `posterior` among the estimators '
             f'(-e), which are: {" ".join(ests)}')
+    if getattr(args, 'posterior_genotypes', False) \
+            and 'posterior' not in ests:
+        raise SystemExit('-pg / --posterior_genotypes writes tables of the '
+            'posterior samples: it needs `posterior` among the estimators '
+            f'(-e), which are: {" ".join(ests)}')
 
 
 def save_outputs(args, results, data, out_dir, names=None):
@@ -175,7 +191,8 @@ def save_outputs(args, results, data, out_dir, names=None):
             # the reference's per-chain posterior (-sc) indexes its parameter
             # trace inconsistently (utils.py:228-229); chains are pooled here
             inf = postproc.posterior_estimate(results, data,
-                support=getattr(args, 'posterior_support', False))
+                support=getattr(args, 'posterior_support', False),
+                cells=getattr(args, 'posterior_genotypes', False))
             rows_a.append(('mean', est,
                 ' '.join(str(i) for i in inf['assignment'])))
             inferred.append(('mean', est, inf))
@@ -213,7 +230,8 @@ def save_outputs(args, results, data, out_dir, names=None):
         for key, val in vars(args).items():
             if key == 'time':
                 val = [f'{t:%Y%m%d_%H:%M:%S}' for t in val]
-            if key == 'posterior_support' and not val:
+            if key in ('posterior_support', 'posterior_genotypes') \
+                    and not val:
                 continue        # listed only when it is set
             f.write(f'{key}: {val}\n')
     mut_names = names[1] if names is not None else None
@@ -223,6 +241,9 @@ def save_outputs(args, results, data, out_dir, names=None):
         if 'support' in inf:
             bio.save_support(out_dir, chain, est, inf['support'],
                 inf['assignment'], names[0] if names is not None else None)
+        if 'cell_genotypes' in inf:
+            bio.save_cell_geno(out_dir, chain, est, inf['cell_genotypes'],
+                names)
     # the metric tables list their rows chain by chain, as the reference
     # does (its per-chain dictionary, dpmmIO.py:524-530); the pooled
     # posterior first

@@ -14,7 +14,17 @@ SUPPORT=1: right after the pair counts are made, the three passes that read
 all of them - k_differ_sum, one k_mpear_sums pass, the support pass
 (k_post_support) - beside each other on that matrix for the C true clusters,
 by device events (Posterior.pass_times), and Posterior.support as a call
-(table to the host included) checked against the two others; then exit."""
+(table to the host included) checked against the two others; then exit.
+CELLS_M=<mutations>: right after the pair counts are made, the per-cell
+genotype pass (bnpc_post_cell_genotypes) with a random float32 trace of
+CELLS_W (default C + 8) rows per sample, CELLS_CHUNK samples per upload and
+CELLS_SLAB cells per pass over the trace (0: the defaults): CELLS_REPS
+(default 5) calls without the tables' way back, each by device events
+(Posterior.cell_genotypes_times) - the fastest one's trace uploads, rank
+kernel and accumulation kernel, the element-steps per second of the kernels
+against the device's FP64 vector add rate, the uploads' share - then the call
+with its three tables brought to the host, and - CELLS_HOST=1 - the host loop
+(postproc.host_cell_genotypes) compared with it; then exit."""
 import os
 import sys
 import time
@@ -65,6 +75,51 @@ if os.environ.get('SUPPORT') == '1':
     print('  sum == 2 differ_sum:', int(differ_to.sum()) == 2 * post.differ_sum,
         '; own == 2 mpear sum:', int(differ_to[np.arange(N), labels].sum())
         == 2 * int(post.mpear_sums(labels[None])[0]))
+    post.close()
+    sys.exit(0)
+CELLS_M = int(os.environ.get('CELLS_M', '0'))
+if CELLS_M:
+    # FP64 vector adds per second: 256 compute units x 4 SIMDs x 32 lanes at
+    # 2.4 GHz retire one float32 operation per lane and cycle (157.3 TFLOPS
+    # of FMA), a float64 one every other cycle
+    F64_ADDS = 256 * 4 * 32 * 2.4e9 / 2
+    W = int(os.environ.get('CELLS_W', str(C + 8)))
+    chunk = int(os.environ.get('CELLS_CHUNK', '0'))
+    slab = int(os.environ.get('CELLS_SLAB', '0'))
+    reps = int(os.environ.get('CELLS_REPS', '5'))
+    params = np.empty((S, W, CELLS_M), dtype=np.float32)
+    for s in range(S):
+        params[s] = rng.random_sample((W, CELLS_M))
+    steps = N * CELLS_M * S
+    print(f'cell genotypes: M={CELLS_M} W={W} chunk={chunk} slab={slab}, '
+        f'trace {params.nbytes / 1e9:.2f} GB, tables '
+        f'{N * CELLS_M * 20 / 1e9:.2f} GB, {steps:.3e} element-steps')
+    runs = []
+    for r in range(reps):
+        t0 = time.perf_counter()
+        t_up, t_rank, t_acc = post.cell_genotypes_times(params, chunk, slab)
+        wall = time.perf_counter() - t0
+        runs.append((t_up + t_rank + t_acc, t_up, t_rank, t_acc, wall))
+        print(f'  rep {r}: uploads {t_up:.4f} s  k_cg_rank {t_rank:.4f} s  '
+            f'k_cg_accum {t_acc:.4f} s  (host clock, whole call {wall:.4f} s)',
+            flush=True)
+    total, t_up, t_rank, t_acc, wall = min(runs)
+    kern = t_rank + t_acc
+    print(f'  fastest of {reps} (device events): pass {total:.4f} s = uploads '
+        f'{t_up:.4f} s ({100 * t_up / total:.1f} %) + kernels {kern:.4f} s')
+    print(f'    kernels: {steps / kern:.3e} element-steps/s = '
+        f'{100 * steps / kern / F64_ADDS:.1f} % of {F64_ADDS:.3e} FP64 vector '
+        f'adds/s (two float64 operations per element-step: '
+        f'{100 * 2 * steps / kern / F64_ADDS:.1f} %); whole pass '
+        f'{steps / total:.3e} element-steps/s', flush=True)
+    t0 = time.perf_counter()
+    got = post.cell_genotypes(params, chunk, slab)
+    t0 = lap('Posterior.cell_genotypes (call, three tables to the host)', t0)
+    if os.environ.get('CELLS_HOST') == '1':
+        want = postproc.host_cell_genotypes(a, params)
+        t0 = lap('host loop (postproc.host_cell_genotypes)', t0)
+        print('  device == host:', all(np.array_equal(g, w)
+            for g, w in zip(got, want)))
     post.close()
     sys.exit(0)
 tree = post.ward()
