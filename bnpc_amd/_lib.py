@@ -313,6 +313,10 @@ SIGNATURES = {
         _i64, _pd, _pd, C.c_void_p]),
     'bnpc_post_cell_genotypes_times': (C.c_int, [C.c_void_p, _pf, _i64, _i64,
         _i64, _i64, C.POINTER(C.c_float)]),
+    'bnpc_post_cell_fit': (C.c_int, [C.c_void_p, C.c_void_p, _pf, _i64, _i64,
+        _pd, _pd, _i64, _i64, _pd, _pd, _pd, _pd]),
+    'bnpc_post_cell_fit_times': (C.c_int, [C.c_void_p, C.c_void_p, _pf, _i64,
+        _i64, _pd, _pd, _i64, _i64, C.POINTER(C.c_float)]),
     'bnpc_post_ward': (C.c_int, [C.c_void_p, _pd]),
     'bnpc_post_ward_stats': (C.c_int, [C.c_void_p, C.POINTER(_i64),
         C.POINTER(_i64)]),
@@ -655,6 +659,22 @@ def ward_finish(raw, n):
     return Z
 
 
+def data_codes(data):
+    """cells x mutations uint8 codes of a data matrix: 1, 0, and 3 for a
+    missing entry (NaN or 3); any other value becomes 2, which no consumer
+    takes.  A uint8 array is taken as the codes themselves."""
+    data = np.asarray(data)
+    if data.dtype == np.uint8:
+        return np.ascontiguousarray(data)
+    codes = np.full(data.shape, 2, dtype=np.uint8)
+    codes[data == 0] = 0
+    codes[data == 1] = 1
+    codes[data == 3] = 3
+    if data.dtype.kind == 'f':
+        codes[np.isnan(data)] = 3
+    return codes
+
+
 class Posterior:
     """Device-resident pair counts of a set of posterior samples (bnpc_post):
     differ[(i, j)] = samples in which cells i and j carry different labels,
@@ -799,6 +819,48 @@ class Posterior:
         check(load().bnpc_post_cell_genotypes_times(self._h, ptr(par),
             par.shape[1], par.shape[2], int(chunk), int(slab), ms),
             'post_cell_genotypes_times')
+        return tuple(x / 1e3 for x in ms)
+
+    def _fit_args(self, data, params, FN, FP):
+        par = self._trace(params)
+        codes = data_codes(data)
+        if codes.shape != (self.N, par.shape[2]):
+            raise ValueError(f'the data must be {self.N} cells x '
+                f'{par.shape[2]} mutations, not {codes.shape}')
+        rates = [np.ascontiguousarray(x, dtype=np.float64) for x in (FN, FP)]
+        if any(x.shape != (self.S,) for x in rates):
+            raise ValueError(f'FN and FP must hold {self.S} samples each')
+        return codes, par, rates[0], rates[1]
+
+    def cell_fit(self, data, params, FN, FP, chunk=0, slab=0, matrix=False):
+        """The pointwise log-likelihood of every cell in every posterior
+        sample, reduced per cell (bnpc_post_cell_fit) -> (mean, m2, lme, ll):
+        (N,) float64 each, as postproc.host_cell_fit defines them, and - with
+        matrix=True, else None - the (S, N) matrix ll itself.  data: cells x
+        mutations, 0 / 1 / missing (NaN or 3), or its uint8 codes 0 | 1 | 3;
+        params: the samples x W x M trace; FN, FP: the S error rates of the
+        samples, strictly inside (0, 1).  chunk: samples per upload (0: about
+        512 MB of trace and tables); slab: cells per pass over the trace (0:
+        what the free device memory takes).  The same bits for any chunk and
+        slab."""
+        codes, par, FN, FP = self._fit_args(data, params, FN, FP)
+        mean, m2, lme = (np.empty(self.N) for _ in range(3))
+        ll = np.empty((self.S, self.N)) if matrix else None
+        check(load().bnpc_post_cell_fit(self._h, ptr(codes), ptr(par),
+            par.shape[1], par.shape[2], ptr(FN), ptr(FP), int(chunk),
+            int(slab), ptr(mean), ptr(m2), ptr(lme),
+            None if ll is None else ptr(ll)), 'post_cell_fit')
+        return mean, m2, lme, ll
+
+    def cell_fit_times(self, data, params, FN, FP, chunk=0, slab=0):
+        """Seconds by device events, summed over one cell_fit call that
+        brings nothing back: (uploads of bit planes and trace, rank kernel,
+        table kernel, sums kernel, per-cell reduction)."""
+        codes, par, FN, FP = self._fit_args(data, params, FN, FP)
+        ms = (C.c_float * 5)()
+        check(load().bnpc_post_cell_fit_times(self._h, ptr(codes), ptr(par),
+            par.shape[1], par.shape[2], ptr(FN), ptr(FP), int(chunk),
+            int(slab), ms), 'post_cell_fit_times')
         return tuple(x / 1e3 for x in ms)
 
     def close(self):

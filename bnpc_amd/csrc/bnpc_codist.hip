@@ -2076,3 +2076,403 @@ extern "C" int bnpc_post_cell_genotypes_times(bnpc_post *p,
     }
     return cg_run(p, params, W, M, chunk, slab, nullptr, nullptr, nullptr, ms);
 }
+
+// ---------------------------------------------------------------------------
+// Per-cell posterior fit (-pf): the pointwise log-likelihood of every cell in
+// every posterior sample and its per-cell reductions.  With r_s(i) the row of
+// cell i's cluster in sample s (k_cg_rank), th = P[s][r][m] (float32),
+// t = (double)th and o = (double)(1.0f - th),
+//   L1 = log(t * (1 - FN[s]) + o * FP[s])   L0 = log(t * FN[s] + o * (1 - FP[s]))
+// (the expressions of k_tables_theta, every operation rounded on its own),
+//   ll[s][i] = sum over m of L1[s][r][m] where the cell shows a 1, L0 where
+//              it shows a 0, nothing where the entry is missing
+// and per cell, over its column of ll one sample at a time in increasing s:
+// mean = (sum from 0.0) / S, m2 = sum of (ll - mean)^2,
+// lme = mx + log(sum of exp(ll - mx)) - log(S) with mx the column's maximum.
+// postproc.host_cell_fit is the host loop this is pinned to: mean and m2 bit
+// for bit on the returned ll; ll itself to the rounding of a sum over the
+// mutations in another order (no atomics: the same bits on every call).
+//
+// Per slab of cells the data go up once as two bit planes (is-1, is-0), 32
+// mutations to a word pair; per chunk of the trace, three launches:
+// k_cg_rank    the slab's ranks of the chunk's samples (as for -pg)
+// k_cf_tables  thread = one (sample, row, mutation) of the chunk: L1 and L0 as
+//              float64 [sc][W][M], the rows below the sample's cluster count
+// k_cf_sums    workgroup = (CG_CELLS consecutive cells, sample): the lanes run
+//              along the mutations (512 contiguous bytes of one table row per
+//              wave and load, which all cells of the cluster share from
+//              cache), a lane adds the elements m = lane, lane + 256, ... of
+//              each of its cells into an accumulator of its own, then a fixed
+//              tree over the workgroup (shuffles in the wave, the four waves
+//              in order) and LL[s][cell] of the slab, which stays on the
+//              device over all chunks
+// and after the last chunk
+// k_cf_reduce  thread = cell: two walks down its S values of LL.
+// LL resident (S x slab x 8 bytes) is what makes the reductions independent
+// of the chunking: mean is needed before m2 and the maximum before the
+// exp-sum, over all the samples.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_cf_tables(
+    const float *__restrict__ P, int sc, int W, long long M,
+    const int *__restrict__ distinct, const double *__restrict__ FN,
+    const double *__restrict__ FP, double *__restrict__ L1,
+    double *__restrict__ L0)
+{
+    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+    for (int q = blockIdx.y; q < sc; q += gridDim.y) {
+        if (idx >= (long long)distinct[q] * M) continue;
+        const size_t at = (size_t)q * W * M + idx;
+        const double fn = FN[q], fp = FP[q];
+        const float th = P[at];
+        const double th64 = (double)th;
+        const double om64 = (double)(1.0f - th);
+        L1[at] = log(th64 * (1.0 - fn) + om64 * fp);
+        L0[at] = log(th64 * fn + om64 * (1.0 - fp));
+    }
+}
+
+// one chunk of sc samples, the first of them sample s0: L1 / L0 its tables,
+// rank its [sc][pitch] rows (pitch a multiple of CG_CELLS, the padding cells
+// rank 0), planes the slab's [pitch][nwm] word pairs (x: is-1, y: is-0; the
+// padding cells and the bits past M zero), LL the slab's [S][pitch]
+__global__ __launch_bounds__(256) void k_cf_sums(
+    const double *__restrict__ L1, const double *__restrict__ L0, int sc,
+    int W, long long M, const unsigned short *__restrict__ rank,
+    long long pitch, long long nc, const uint2 *__restrict__ planes,
+    long long nwm, long long s0, double *__restrict__ LL)
+{
+    __shared__ double part[4][CG_CELLS];
+    const int tid = threadIdx.x;
+    const long long c0 = (long long)blockIdx.x * CG_CELLS;
+    const uint2 *pl = planes + (size_t)c0 * nwm;
+    for (int q = blockIdx.y; q < sc; q += gridDim.y) {
+        // the workgroup's CG_CELLS ranks: 16 aligned bytes, the same address
+        // in every lane
+        const uint4 packed = *(const uint4 *)(rank + (size_t)q * pitch + c0);
+        const unsigned r2[4] = {packed.x, packed.y, packed.z, packed.w};
+        const double *t1[CG_CELLS], *t0[CG_CELLS];
+        double acc[CG_CELLS];
+#pragma unroll
+        for (int c = 0; c < CG_CELLS; c++) {
+            const unsigned r = (r2[c >> 1] >> (16 * (c & 1))) & 0xffffu;
+            const size_t row = ((size_t)q * W + r) * M;
+            t1[c] = L1 + row;
+            t0[c] = L0 + row;
+            acc[c] = 0.0;
+        }
+        for (long long m = tid; m < M; m += 256) {
+            const unsigned bit = 1u << (m & 31);
+            double v[CG_CELLS];
+#pragma unroll
+            for (int c = 0; c < CG_CELLS; c++) {
+                const uint2 w = pl[(size_t)c * nwm + (m >> 5)];
+                const double *src = (w.x & bit) ? t1[c] : t0[c];
+                v[c] = ((w.x | w.y) & bit) ? src[m] : 0.0;
+            }
+#pragma unroll
+            for (int c = 0; c < CG_CELLS; c++) acc[c] += v[c];
+        }
+#pragma unroll
+        for (int c = 0; c < CG_CELLS; c++) {
+            double v = acc[c];
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+            if ((tid & 63) == 0) part[tid >> 6][c] = v;
+        }
+        __syncthreads();
+        if (tid < CG_CELLS && c0 + tid < nc)
+            LL[(size_t)(s0 + q) * pitch + c0 + tid] =
+                ((part[0][tid] + part[1][tid]) + part[2][tid]) + part[3][tid];
+        __syncthreads();                    // part is reused
+    }
+}
+
+// cell i of the slab: its column LL[0 .. S)[i] in increasing s
+__global__ __launch_bounds__(256) void k_cf_reduce(
+    const double *__restrict__ LL, long long S, long long pitch, long long nc,
+    double *__restrict__ mean, double *__restrict__ m2,
+    double *__restrict__ lme)
+{
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= nc) return;
+    const double *col = LL + i;
+    double mx = col[0], acc = 0.0;
+    for (long long s = 0; s < S; s++) {
+        const double v = col[(size_t)s * pitch];
+        mx = v > mx ? v : mx;
+        acc += v;
+    }
+    const double mu = acc / (double)S;
+    double dev = 0.0, es = 0.0;
+    for (long long s = 0; s < S; s++) {
+        const double v = col[(size_t)s * pitch];
+        dev += (v - mu) * (v - mu);
+        es += exp(v - mx);
+    }
+    mean[i] = mu;
+    m2[i] = dev;
+    lme[i] = (mx + log(es)) - log((double)S);
+}
+
+// ms (NULL, or 5 floats): device-event milliseconds summed over the call -
+// ms[0] the uploads (bit planes and trace), ms[1] k_cg_rank, ms[2]
+// k_cf_tables, ms[3] k_cf_sums, ms[4] k_cf_reduce
+static int cf_run(bnpc_post *p, const uint8_t *codes, const float *params,
+                  int64_t W, int64_t M, const double *FN, const double *FP,
+                  int64_t chunk, int64_t slab, double *mean, double *m2,
+                  double *lme, double *ll, float *ms)
+{
+    if (!p || !codes || !params || !FN || !FP || W < 1
+        || W >= (int64_t)GT_MIXED || M < 1
+        || (W * M + 255) / 256 > (int64_t)INT_MAX || chunk < 0 || slab < 0) {
+        bnpc_set_error("bad argument: the cell fit needs the data's codes, a "
+                       "1 <= W < 65534 x M >= 1 trace, FN, FP, chunk >= 0 and "
+                       "slab >= 0");
+        return 2;
+    }
+    if (!p->assign || !p->labels_in_range) {
+        bnpc_set_error("cell fit: the sample labels must lie in [0, N = %lld)",
+                       (long long)p->N);
+        return 2;
+    }
+    const int64_t S = p->S, N = p->N;
+    for (int64_t s = 0; s < S; s++) {
+        if (!(FN[s] > 0.0 && FN[s] < 1.0 && FP[s] > 0.0 && FP[s] < 1.0)) {
+            bnpc_set_error("cell fit: FN = %g, FP = %g of sample %lld are not "
+                           "both inside (0, 1)", FN[s], FP[s], (long long)s);
+            return 2;
+        }
+    }
+    // the two bit planes of every cell, 32 mutations to a word pair
+    const int64_t nwm = (M + 31) / 32;
+    std::vector<uint2> planes((size_t)N * nwm, make_uint2(0u, 0u));
+    for (int64_t i = 0; i < N; i++) {
+        const uint8_t *row = codes + (size_t)i * M;
+        uint2 *out = planes.data() + (size_t)i * nwm;
+        for (int64_t m = 0; m < M; m++) {
+            const uint8_t c = row[m];
+            if (c == 1) {
+                out[m >> 5].x |= 1u << (m & 31);
+            } else if (c == 0) {
+                out[m >> 5].y |= 1u << (m & 31);
+            } else if (c != 3) {
+                bnpc_set_error("cell fit: code %d of cell %lld at mutation "
+                               "%lld is not 0, 1 or 3", (int)c, (long long)i,
+                               (long long)m);
+                return 2;
+            }
+        }
+    }
+    PCK(hipSetDevice(p->device));
+    GtBuffers buf;
+    CgEvents evs;
+    auto oom = [](hipError_t e) {
+        (void)hipGetLastError();
+        bnpc_set_error("cell fit: out of device memory (%s)",
+                       hipGetErrorString(e));
+        return 5;
+    };
+#define CFA(expr)                                                            \
+    do {                                                                     \
+        hipError_t a_ = (expr);                                              \
+        if (a_ == hipErrorOutOfMemory) return oom(a_);                       \
+        PCK(a_);                                                             \
+    } while (0)
+
+    // every sample's cluster count against the trace's rows, before anything
+    // is added up; the table kernel reads the counts too
+    GtArea area;
+    int *d_distinct;
+    CFA(buf.alloc(&d_distinct, S));
+    if ((size_t)cg_rank_words(N) * 4 <= CG_LDS_MAX) {
+        area.grid = (unsigned)std::min<int64_t>(S, 65535);
+        area.lds = (size_t)cg_rank_words(N) * 4;
+    } else {
+        area.grid = (unsigned)std::min<int64_t>(S, GT_GLOBAL_WG);
+        area.stride = cg_rank_words(N);
+        CFA(buf.alloc(&area.scratch, (size_t)area.grid * area.stride));
+    }
+    std::vector<int> distinct(S);
+    for (int64_t s0 = 0; s0 < S; s0 += INT_MAX) {
+        const int64_t n = std::min<int64_t>(INT_MAX, S - s0);
+        hipLaunchKernelGGL(k_cg_rank, dim3(area.grid), dim3(256), area.lds, 0,
+                           p->assign, (long long)s0, (int)n, (long long)N, 0LL,
+                           0LL, 0LL, area.scratch, area.stride,
+                           (unsigned short *)nullptr, d_distinct + s0);
+        PCK(hipGetLastError());
+    }
+    PCK(hipMemcpy(distinct.data(), d_distinct, S * sizeof(int),
+                  hipMemcpyDeviceToHost));
+    for (int64_t s = 0; s < S; s++) {
+        if (distinct[s] > W) {
+            bnpc_set_error("cell fit: sample %lld has %d clusters, the trace "
+                           "%lld rows", (long long)s, distinct[s],
+                           (long long)W);
+            return 2;
+        }
+    }
+
+    // the chunk of the trace and its two tables (20 bytes per parameter),
+    // then as many cells as fit beside them
+    const size_t sample_floats = (size_t)W * M;
+    int64_t sc = chunk;
+    if (sc == 0)
+        sc = std::max<int64_t>(1, (int64_t)(((size_t)512 << 20)
+                                            / (sample_floats * 20)));
+    sc = std::min<int64_t>(std::min(sc, S), INT_MAX);
+    float *d_P;
+    double *d_L1, *d_L0, *d_FN, *d_FP;
+    CFA(buf.alloc(&d_P, (size_t)sc * sample_floats));
+    CFA(buf.alloc(&d_L1, (size_t)sc * sample_floats));
+    CFA(buf.alloc(&d_L0, (size_t)sc * sample_floats));
+    CFA(buf.alloc(&d_FN, (size_t)S));
+    CFA(buf.alloc(&d_FP, (size_t)S));
+    size_t free_b = 0, total_b = 0;
+    PCK(hipMemGetInfo(&free_b, &total_b));
+    // per cell: its column of LL, its bit planes, its ranks and the three
+    // results (the pitch rounds up)
+    const size_t per_cell = (size_t)S * 8 + (size_t)nwm * 8 + (size_t)sc * 2
+        + 24;
+    const size_t margin = ((size_t)64 << 20) + per_cell * CG_CELLS;
+    const size_t room = free_b > margin ? (free_b - margin) / per_cell : 0;
+    int64_t nc = slab ? std::min(slab, N)
+                      : (int64_t)std::min<size_t>((size_t)N, room);
+    if (nc < 1 || (size_t)nc > room) {
+        bnpc_set_error("cell fit: a slab of %lld cells x %lld samples needs "
+                       "%.1f GB, %.1f GB of device memory are free",
+                       (long long)std::max<int64_t>(nc, 1), (long long)S,
+                       (double)std::max<int64_t>(nc, 1) * per_cell / 1e9,
+                       free_b / 1e9);
+        return 5;
+    }
+    const int64_t pitch = (nc + CG_CELLS - 1) / CG_CELLS * CG_CELLS;
+    unsigned short *d_rank;
+    uint2 *d_planes;
+    double *d_LL, *d_out;
+    CFA(buf.alloc(&d_rank, (size_t)sc * pitch));
+    CFA(buf.alloc(&d_planes, (size_t)pitch * nwm));
+    CFA(buf.alloc(&d_LL, (size_t)S * pitch));
+    CFA(buf.alloc(&d_out, (size_t)3 * nc));
+#undef CFA
+    // (the padding cells of a row keep rank 0, a row every trace has, and
+    // empty planes)
+    PCK(hipMemset(d_rank, 0, (size_t)sc * pitch * sizeof(unsigned short)));
+    PCK(hipMemset(d_planes, 0, (size_t)pitch * nwm * sizeof(uint2)));
+    PCK(hipMemcpy(d_FN, FN, S * sizeof(double), hipMemcpyHostToDevice));
+    PCK(hipMemcpy(d_FP, FP, S * sizeof(double), hipMemcpyHostToDevice));
+    if (ms) {
+        for (int k = 0; k < 5; k++) ms[k] = 0.0f;
+        PCK(hipEventCreate(&evs.ev[0]));
+        PCK(hipEventCreate(&evs.ev[1]));
+    }
+    // a lap of the device's clock: begin(), the work, end(its slot of ms)
+    int lap_rc = 0;
+    auto begin = [&]() {
+        if (ms && hipEventRecord(evs.ev[0], 0) != hipSuccess) lap_rc = 1;
+    };
+    auto end = [&](int which) {
+        if (!ms) return;
+        float t = 0.0f;
+        if (hipEventRecord(evs.ev[1], 0) != hipSuccess
+            || hipEventSynchronize(evs.ev[1]) != hipSuccess
+            || hipEventElapsedTime(&t, evs.ev[0], evs.ev[1]) != hipSuccess)
+            lap_rc = 1;
+        ms[which] += t;
+    };
+    const unsigned table_blocks = (unsigned)((W * M + 255) / 256);
+    for (int64_t i0 = 0; i0 < N; i0 += nc) {
+        const int64_t cells = std::min(nc, N - i0);
+        const unsigned tiles = (unsigned)((cells + CG_CELLS - 1) / CG_CELLS);
+        begin();
+        PCK(hipMemcpy(d_planes, planes.data() + (size_t)i0 * nwm,
+                      (size_t)cells * nwm * sizeof(uint2),
+                      hipMemcpyHostToDevice));
+        // (a last, shorter slab: its tile's padding cells are empty too)
+        if (cells < pitch)
+            PCK(hipMemset(d_planes + (size_t)cells * nwm, 0,
+                          (size_t)(pitch - cells) * nwm * sizeof(uint2)));
+        end(0);
+        for (int64_t s0 = 0; s0 < S; s0 += sc) {
+            const int64_t n = std::min(sc, S - s0);
+            const unsigned rows = (unsigned)std::min<int64_t>(n, 65535);
+            begin();
+            PCK(hipMemcpy(d_P, params + (size_t)s0 * sample_floats,
+                          (size_t)n * sample_floats * sizeof(float),
+                          hipMemcpyHostToDevice));
+            end(0);
+            begin();
+            hipLaunchKernelGGL(k_cg_rank,
+                               dim3((unsigned)std::min<int64_t>(n, area.grid)),
+                               dim3(256), area.lds, 0, p->assign,
+                               (long long)s0, (int)n, (long long)N,
+                               (long long)i0, (long long)cells,
+                               (long long)pitch, area.scratch, area.stride,
+                               d_rank, (int *)nullptr);
+            PCK(hipGetLastError());
+            end(1);
+            begin();
+            hipLaunchKernelGGL(k_cf_tables, dim3(table_blocks, rows),
+                               dim3(256), 0, 0, d_P, (int)n, (int)W,
+                               (long long)M, d_distinct + s0, d_FN + s0,
+                               d_FP + s0, d_L1, d_L0);
+            PCK(hipGetLastError());
+            end(2);
+            begin();
+            hipLaunchKernelGGL(k_cf_sums, dim3(tiles, rows), dim3(256), 0, 0,
+                               d_L1, d_L0, (int)n, (int)W, (long long)M,
+                               d_rank, (long long)pitch, (long long)cells,
+                               d_planes, (long long)nwm, (long long)s0, d_LL);
+            PCK(hipGetLastError());
+            end(3);
+        }
+        begin();
+        hipLaunchKernelGGL(k_cf_reduce, dim3((unsigned)((cells + 255) / 256)),
+                           dim3(256), 0, 0, d_LL, (long long)S,
+                           (long long)pitch, (long long)cells, d_out,
+                           d_out + nc, d_out + 2 * nc);
+        PCK(hipGetLastError());
+        end(4);
+        double *host[3] = {mean, m2, lme};
+        for (int k = 0; k < 3; k++)
+            if (host[k])
+                PCK(hipMemcpy(host[k] + i0, d_out + (size_t)k * nc,
+                              cells * sizeof(double), hipMemcpyDeviceToHost));
+        if (ll)
+            PCK(hipMemcpy2D(ll + i0, (size_t)N * sizeof(double), d_LL,
+                            (size_t)pitch * sizeof(double),
+                            (size_t)cells * sizeof(double), (size_t)S,
+                            hipMemcpyDeviceToHost));
+    }
+    PCK(hipDeviceSynchronize());
+    if (lap_rc) {
+        bnpc_set_error("cell fit: the device events failed");
+        return 1;
+    }
+    return 0;
+}
+
+extern "C" int bnpc_post_cell_fit(bnpc_post *p, const uint8_t *codes,
+                                  const float *params, int64_t W, int64_t M,
+                                  const double *FN, const double *FP,
+                                  int64_t chunk, int64_t slab, double *mean,
+                                  double *m2, double *lme, double *ll)
+{
+    return cf_run(p, codes, params, W, M, FN, FP, chunk, slab, mean, m2, lme,
+                  ll, nullptr);
+}
+
+// diagnostic (tools/posterior_bench.py): one bnpc_post_cell_fit call without
+// its results' way back, by device events (see cf_run)
+extern "C" int bnpc_post_cell_fit_times(bnpc_post *p, const uint8_t *codes,
+                                        const float *params, int64_t W,
+                                        int64_t M, const double *FN,
+                                        const double *FP, int64_t chunk,
+                                        int64_t slab, float *ms)
+{
+    if (!ms) {
+        bnpc_set_error("bad argument: NULL");
+        return 2;
+    }
+    return cf_run(p, codes, params, W, M, FN, FP, chunk, slab, nullptr,
+                  nullptr, nullptr, nullptr, ms);
+}

@@ -326,6 +326,46 @@ def save_cell_geno(out_dir, chain, est, tables, names=None):
     return paths
 
 
+def save_cell_fit(out_dir, chain, est, fit, assignment, names=None):
+    """The -pf files of postproc.cell_fit for one (chain, estimator) row.
+    cell_fit_<est>_<chain>.tsv: per cell its name (`names`, the loader's cell
+    names, when there is one per cell, else 0..N-1), its cluster (the label
+    of `assignment`), its observed entries, the mean and the standard
+    deviation of its log-likelihood over the samples, its share of lppd and
+    of p_waic, and the mean log-likelihood per observed entry; floats %.4f.
+    model_fit_<est>_<chain>.txt: `key: value` lines - samples, cells,
+    observations, lppd, p_waic, WAIC (= -2 (lppd - p_waic); the unit is the
+    cell) and worst_cells, the ten cells with the smallest mean
+    log-likelihood per observed entry as name:value pairs."""
+    assignment = np.asarray(assignment)
+    N = assignment.size
+    index = np.arange(N)
+    if names is not None and np.asarray(names).size == N:
+        index = np.asarray(names)
+    index = index.tolist()
+    tag = f'{chain:0>2}'
+    paths = [os.path.join(out_dir, f'cell_fit_{est}_{tag}.tsv'),
+        os.path.join(out_dir, f'model_fit_{est}_{tag}.txt')]
+    columns = ('mean_ll', 'sd_ll', 'lppd', 'p_waic', 'mean_ll_per_obs')
+    with open(paths[0], 'w') as f:
+        f.write('cell\tcluster\tn_obs\t' + '\t'.join(columns) + '\n')
+        for i, name in enumerate(index):
+            f.write(f'{name}\t{assignment[i]}\t{fit["n_obs"][i]}\t'
+                + '\t'.join(f'{fit[k][i]:.4f}' for k in columns) + '\n')
+    total = fit['total']
+    per_obs = fit['mean_ll_per_obs']
+    worst = np.argsort(per_obs, kind='stable')[:10]
+    with open(paths[1], 'w') as f:
+        for key in ('samples', 'cells', 'observations'):
+            f.write(f'{key}: {total[key]}\n')
+        for key, val in (('lppd', total['lppd']), ('p_waic', total['p_waic']),
+                ('WAIC', total['waic'])):
+            f.write(f'{key}: {val:.4f}\n')
+        f.write('worst_cells: ' + ' '.join(f'{index[i]}:{per_obs[i]:.4f}'
+            for i in worst.tolist()) + '\n')
+    return paths
+
+
 def save_metric(path, column, rows):
     """V_measure.txt / ARI.txt / hammingDist.txt (dpmmIO.py:514-542): a
     tab-separated `chain  estimator  <column>` table, floats as to_csv

@@ -20,6 +20,10 @@ cluster a cell was in, averaged over the samples - not a reference output)
 are a device pass over the samples and the parameter trace
 (bnpc_post_cell_genotypes; host_cell_genotypes is the host loop it is pinned
 to).
+The -pf tables (per-cell posterior fit and the run's WAIC, from the pointwise
+log-likelihood of every cell in every sample - not a reference output) are a
+device pass over the samples, the parameter trace and the data
+(bnpc_post_cell_fit; host_cell_fit is the host loop it is pinned to).
 The -tc / -td metrics (V-measure, ARI, Hamming; utils.py:49-72) are
 restated from integer counts at the end; tree helpers are out of scope.
 """
@@ -384,22 +388,27 @@ def concat_chain_results(results):
     return pooled
 
 
-def posterior_estimate(results, data, support=False, cells=False):
+def posterior_estimate(results, data, support=False, cells=False, fit=False):
     """`-e posterior` (the default estimator), chains pooled
     (utils.py:195-244).  support=True: the key 'support' holds the tables of
     cluster_support for the MPEAR clustering, made from the pair counts of
     the MPEAR scoring while they are still on the device.  cells=True: the
     key 'cell_genotypes' holds the tables of cell_genotypes, made from the
-    samples the same handle keeps on the device."""
+    samples the same handle keeps on the device.  fit=True: the key 'fit'
+    holds the tables of cell_fit, from the same samples, the data and the
+    samples' error rates."""
     res = concat_chain_results(results)
     tables = {}
-    if support or cells:
+    if support or cells or fit:
         def while_open(post, assign):
             if support:
                 tables['support'] = posterior_support(post, assign)
             if cells:
                 tables['cell_genotypes'] = cell_genotypes(post,
                     res['assignments'], res['params'])
+            if fit:
+                tables['fit'] = cell_fit(post, data, res['assignments'],
+                    res['params'], res['FN'], res['FP'])
     else:
         while_open = None
     assign, params = _mean_hierarchy(res['assignments'], res['params'],
@@ -543,6 +552,107 @@ def cell_genotypes(post, assignments, params_full):
     mean = sum1 / S
     sd = np.sqrt(np.maximum(sum2 / S - mean * mean, 0))
     return {'mean': mean, 'sd': sd, 'prob': ones / S}
+
+
+# ---------------------------------------------------------------------------
+# per-cell posterior fit and WAIC (-pf): how well the model explains every
+# cell, from the pointwise log-likelihood of every cell in every sample; not
+# a reference output, so the arithmetic and the summation order below are the
+# specification
+# ---------------------------------------------------------------------------
+def data_codes(data):
+    """cells x mutations uint8: 1, 0, and 3 for a missing entry (NaN or 3 in
+    `data`); any other value raises ValueError."""
+    from bnpc_amd import _lib
+    codes = _lib.data_codes(data)
+    if not np.isin(codes, (0, 1, 3)).all():
+        raise ValueError('the data must be 0, 1 or missing (NaN or 3)')
+    return codes
+
+
+def host_cell_fit(data, assignments, params_full, FN, FP):
+    """The pointwise log-likelihood of every cell in every posterior sample
+    and its per-cell reductions; the plain loop bnpc_post_cell_fit is pinned
+    to.  data: cells x mutations, 0 / 1 / missing (NaN or 3); assignments:
+    S x N, any integer labels; params_full: S x W x M, the row of a cell in
+    sample s the rank of its label among the sample's distinct labels (as in
+    host_cell_genotypes); FN, FP: the S error rates of the samples.  With
+    th = float32 params_full[s][r][m], t = float64(th) and
+    o = float64(float32(1) - th),
+      L1 = log(t * (1 - FN[s]) + o * FP[s])     an observed 1
+      L0 = log(t * FN[s] + o * (1 - FP[s]))     an observed 0
+    (the expressions of k_tables_theta, each operation rounded on its own),
+    ll[s][i] is the sum over the mutations of L1 where the cell shows a 1 and
+    L0 where it shows a 0.  Per cell, over the column ll[:, i] one sample at
+    a time in increasing s: mean (the sum from 0.0, divided by S), m2 (the
+    sum of (ll - mean)**2), lme = mx + log(sum of exp(ll - mx)) - log(S) with
+    mx the column's maximum - the log of the mean likelihood; n_obs counts
+    the cell's observed entries.
+    -> {'ll': (S, N), 'mean', 'm2', 'lme': (N,) float64, 'n_obs': (N,) int64}
+    """
+    codes = data_codes(data)
+    assignments = np.asarray(assignments)
+    S, N = assignments.shape
+    FN = np.asarray(FN, dtype=np.float64)
+    FP = np.asarray(FP, dtype=np.float64)
+    ll = np.empty((S, N))
+    for s in range(S):
+        rank = np.unique(assignments[s], return_inverse=True)[1].ravel()
+        th = np.asarray(params_full[s], dtype=np.float32)[:rank.max() + 1]
+        t = th.astype(np.float64)
+        o = (np.float32(1) - th).astype(np.float64)
+        L1 = np.log(t * (1 - FN[s]) + o * FP[s])
+        L0 = np.log(t * FN[s] + o * (1 - FP[s]))
+        # (where: an entry that is not there adds nothing, whatever its log)
+        el = np.where(codes == 1, L1[rank], np.where(codes == 0, L0[rank], 0))
+        ll[s] = el.sum(axis=1)
+    acc = np.zeros(N)
+    for s in range(S):
+        acc += ll[s]
+    mean = acc / S
+    m2 = np.zeros(N)
+    for s in range(S):
+        m2 += (ll[s] - mean) ** 2
+    mx = ll.max(axis=0)
+    esum = np.zeros(N)
+    for s in range(S):
+        esum += np.exp(ll[s] - mx)
+    lme = mx + np.log(esum) - np.log(S)
+    return {'ll': ll, 'mean': mean, 'm2': m2, 'lme': lme,
+        'n_obs': (codes != 3).sum(axis=1).astype(np.int64)}
+
+
+def cell_fit(post, data, assignments, params_full, FN, FP):
+    """The -pf tables: how well the model explains every cell, and WAIC
+    (Watanabe 2010; Gelman, Hwang & Vehtari 2014) of the run.  The unit of
+    WAIC here is the cell - its whole row of the matrix is one observation,
+    ll[s][i] its pointwise log-likelihood - not the single entry.  Per cell,
+    (N,) arrays: 'mean_ll' and 'sd_ll' (sqrt(m2 / (S - 1)); 0 for S = 1) of
+    ll over the samples, 'lppd' (the log of the mean likelihood), 'p_waic'
+    (the sample variance m2 / (S - 1); 0 for S = 1), 'n_obs',
+    'mean_ll_per_obs' (mean_ll / n_obs; 0 for a cell without observations).
+    'total': {'samples', 'cells', 'observations', 'lppd', 'p_waic', 'waic'}
+    with waic = -2 (lppd - p_waic), the sums over the cells.  From an open
+    clustering handle: the device pass (Posterior.cell_fit) where the handle
+    has one, else the host loop (host_cell_fit); the same arithmetic on
+    (mean, m2, lme) either way."""
+    device = getattr(post, 'cell_fit', None)
+    if device is not None:
+        mean, m2, lme, _ = device(data, params_full, FN, FP)
+        n_obs = (data_codes(data) != 3).sum(axis=1).astype(np.int64)
+    else:
+        fit = host_cell_fit(data, assignments, params_full, FN, FP)
+        mean, m2, lme, n_obs = (fit[k] for k in ('mean', 'm2', 'lme', 'n_obs'))
+    S, N = np.asarray(assignments).shape
+    var = m2 / (S - 1) if S > 1 else np.zeros(N)
+    per_obs = np.zeros(N)
+    np.divide(mean, n_obs, out=per_obs, where=n_obs > 0)
+    lppd, p_waic = float(lme.sum()), float(var.sum())
+    return {'mean_ll': mean, 'sd_ll': np.sqrt(var), 'lppd': lme,
+        'p_waic': var, 'n_obs': n_obs, 'mean_ll_per_obs': per_obs,
+        'total': {'samples': int(S), 'cells': int(N),
+            'observations': int(n_obs.sum()), 'lppd': lppd, 'p_waic': p_waic,
+            'waic': -2 * (lppd - p_waic)}}
 
 
 # ---------------------------------------------------------------------------

@@ -1071,6 +1071,45 @@ int bnpc_post_cell_genotypes(bnpc_post *post, const float *params, int64_t W,
 int bnpc_post_cell_genotypes_times(bnpc_post *post, const float *params,
                                    int64_t W, int64_t M, int64_t chunk,
                                    int64_t slab, float *ms);
+/* Per-cell posterior fit (-pf; not a reference output): the pointwise
+ * log-likelihood of every cell in every posterior sample, and its per-cell
+ * reductions (WAIC follows on the host, postproc.cell_fit).  With r_s(i) the
+ * row of cell i's cluster in sample s (as bnpc_post_cell_genotypes),
+ * th = params[s][r_s(i)][m], t = (double)th and o = (double)(1.0f - th),
+ *   L1 = log(t * (1 - FN[s]) + o * FP[s]),  L0 = log(t * FN[s] + o * (1 - FP[s]))
+ * (k_tables_theta's expressions, every operation rounded on its own), and
+ *   ll[s][i]  the sum over the mutations of L1 where codes[i][m] == 1 and L0
+ *             where it is 0 (3: missing, nothing); the order of this sum is
+ *             the device's own, the same on every call
+ *   mean[i]   (sum of ll[s][i], one sample at a time in increasing s from 0) / S
+ *   m2[i]     sum of (ll[s][i] - mean[i])^2, in the same order
+ *   lme[i]    mx + log(sum of exp(ll[s][i] - mx)) - log(S), mx the maximum
+ *             over s: the log of the mean likelihood
+ * mean and m2 are bit for bit what bnpc_amd.postproc.host_cell_fit makes of
+ * the returned ll; every output has the same bits for any chunk and slab.
+ * The post's samples must lie in [0, N); params: the S x W x M float32 trace
+ * on the host, W < 65534, streamed `chunk` samples at a time (0: about 512 MB
+ * of trace and tables per chunk); slab: the cells whose S values of ll are on
+ * the device at a time (0: as many as the free device memory takes beside
+ * the chunk) - every slab streams the trace again.  mean, m2, lme (N each)
+ * and ll (S x N) may each be NULL.  Return code 2, and no output written,
+ * for sample labels out of range, a sample with more clusters than the trace
+ * has rows, an FN[s] or FP[s] not strictly inside (0, 1) or a code other
+ * than 0 / 1 / 3; 5 if a slab does not fit the device's free memory. */
+int bnpc_post_cell_fit(bnpc_post *post, const uint8_t *codes /* N x M: 0|1|3 */,
+                       const float *params, int64_t W, int64_t M,
+                       const double *FN, const double *FP /* S each */,
+                       int64_t chunk, int64_t slab,
+                       double *mean, double *m2, double *lme /* N each */,
+                       double *ll /* S x N, or NULL */);
+/* diagnostic: one bnpc_post_cell_fit call without its results' way back,
+ * milliseconds by device events summed over the call - ms[0] the uploads
+ * (bit planes and trace), ms[1] the rank kernel, ms[2] the table kernel,
+ * ms[3] the sums kernel, ms[4] the per-cell reduction */
+int bnpc_post_cell_fit_times(bnpc_post *post, const uint8_t *codes,
+                             const float *params, int64_t W, int64_t M,
+                             const double *FN, const double *FP,
+                             int64_t chunk, int64_t slab, float *ms);
 int bnpc_post_destroy(bnpc_post *post);
 
 #ifdef __cplusplus

@@ -19,7 +19,10 @@ data summed per cluster: cell_support_posterior_mean.tsv and
 cluster_similarity_posterior_mean.tsv; -pg (not a reference flag either)
 writes the per-cell posterior genotypes, averaged over the samples instead of
 taken from the cell's MPEAR cluster: genotypes_cell_prob_posterior_mean.tsv,
-genotypes_cell_cont_posterior_mean.tsv, genotypes_cell_sd_posterior_mean.tsv.
+genotypes_cell_cont_posterior_mean.tsv, genotypes_cell_sd_posterior_mean.tsv;
+-pf (not a reference flag either) writes how well the model explains every
+cell and the run's WAIC, from the log-likelihood of every cell in every
+posterior sample: cell_fit_posterior_mean.tsv, model_fit_posterior_mean.txt.
 """
 import argparse
 from datetime import datetime
@@ -130,6 +133,12 @@ FLAGS = [
         'instead of the genotype of its cluster (needs -e posterior; one '
         'more pass over samples x cells x mutations on the GPU: minutes at '
         '50 000 cells x 5000 mutations).')),
+    ('output', '-pf', '--posterior_fit', dict(action='store_true',
+        default=argparse.SUPPRESS, help='Write how well the model explains '
+        'every cell - mean and spread of its log-likelihood over the '
+        'posterior samples, per observed entry too - and the WAIC of the '
+        'run, with the cell as its unit (needs -e posterior; one more pass '
+        'over samples x cells x mutations on the GPU).')),
 ]
 
 
@@ -138,6 +147,7 @@ class Args(argparse.Namespace):
     parser; a flag of this build alone reads as its default until given."""
     posterior_support = False
     posterior_genotypes = False
+    posterior_fit = False
 
 
 def build_parser():
@@ -175,6 +185,10 @@ def check_args(args):
         raise SystemExit('-pg / --posterior_genotypes writes tables of the '
             'posterior samples: it needs `posterior` among the estimators '
             f'(-e), which are: {" ".join(ests)}')
+    if getattr(args, 'posterior_fit', False) and 'posterior' not in ests:
+        raise SystemExit('-pf / --posterior_fit writes tables of the '
+            'posterior samples: it needs `posterior` among the estimators '
+            f'(-e), which are: {" ".join(ests)}')
 
 
 def save_outputs(args, results, data, out_dir, names=None):
@@ -192,7 +206,8 @@ def save_outputs(args, results, data, out_dir, names=None):
             # trace inconsistently (utils.py:228-229); chains are pooled here
             inf = postproc.posterior_estimate(results, data,
                 support=getattr(args, 'posterior_support', False),
-                cells=getattr(args, 'posterior_genotypes', False))
+                cells=getattr(args, 'posterior_genotypes', False),
+                fit=getattr(args, 'posterior_fit', False))
             rows_a.append(('mean', est,
                 ' '.join(str(i) for i in inf['assignment'])))
             inferred.append(('mean', est, inf))
@@ -204,6 +219,10 @@ def save_outputs(args, results, data, out_dir, names=None):
             if args.verbosity > 0:
                 print(f'posterior: {len(set(inf["assignment"]))} clusters, '
                     f'FN {inf["FN"][0]:.4f}, FP {inf["FP"][0]:.6f}')
+                if 'fit' in inf:
+                    total = inf['fit']['total']
+                    print(f'posterior fit: WAIC {total["waic"]:.4f}, lppd '
+                        f'{total["lppd"]:.4f}, p_waic {total["p_waic"]:.4f}')
             continue
         for chain, res in chains:
             res = res if res is not None else postproc.best_chain(results, est)
@@ -230,8 +249,8 @@ def save_outputs(args, results, data, out_dir, names=None):
         for key, val in vars(args).items():
             if key == 'time':
                 val = [f'{t:%Y%m%d_%H:%M:%S}' for t in val]
-            if key in ('posterior_support', 'posterior_genotypes') \
-                    and not val:
+            if key in ('posterior_support', 'posterior_genotypes',
+                    'posterior_fit') and not val:
                 continue        # listed only when it is set
             f.write(f'{key}: {val}\n')
     mut_names = names[1] if names is not None else None
@@ -244,6 +263,9 @@ def save_outputs(args, results, data, out_dir, names=None):
         if 'cell_genotypes' in inf:
             bio.save_cell_geno(out_dir, chain, est, inf['cell_genotypes'],
                 names)
+        if 'fit' in inf:
+            bio.save_cell_fit(out_dir, chain, est, inf['fit'],
+                inf['assignment'], names[0] if names is not None else None)
     # the metric tables list their rows chain by chain, as the reference
     # does (its per-chain dictionary, dpmmIO.py:524-530); the pooled
     # posterior first

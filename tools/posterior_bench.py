@@ -24,7 +24,13 @@ CELLS_SLAB cells per pass over the trace (0: the defaults): CELLS_REPS
 kernel and accumulation kernel, the element-steps per second of the kernels
 against the device's FP64 vector add rate, the uploads' share - then the call
 with its three tables brought to the host, and - CELLS_HOST=1 - the host loop
-(postproc.host_cell_genotypes) compared with it; then exit."""
+(postproc.host_cell_genotypes) compared with it; then - CELLS_FIT=1 - the
+per-cell fit pass (bnpc_post_cell_fit) over the same trace with random data
+(30 % missing) and error rates, CELLS_REPS calls by device events
+(Posterior.cell_fit_times): the fastest one's uploads and its four kernels,
+the table bytes per second k_cf_sums reads (8 per observed entry, cell and
+sample) beside the trace bytes per second of k_cg_accum (4 per cell, mutation
+and sample), then the call with its results brought to the host; then exit."""
 import os
 import sys
 import time
@@ -120,6 +126,28 @@ if CELLS_M:
         t0 = lap('host loop (postproc.host_cell_genotypes)', t0)
         print('  device == host:', all(np.array_equal(g, w)
             for g, w in zip(got, want)))
+    if os.environ.get('CELLS_FIT') == '1':
+        data = (rng.random_sample((N, CELLS_M)) < 0.3).astype(np.uint8)
+        data[rng.random_sample((N, CELLS_M)) < 0.3] = 3
+        FN, FP = rng.uniform(0.1, 0.3, S), rng.uniform(1e-4, 1e-2, S)
+        seen = int((data != 3).sum()) * S
+        print(f'cell fit: {seen:.3e} observed element-steps of {steps:.3e}, '
+            f'LL {S * N * 8 / 1e9:.2f} GB')
+        runs = []
+        for r in range(reps):
+            t = post.cell_fit_times(data, params, FN, FP, chunk, slab)
+            runs.append((sum(t),) + t)
+            print(f'  rep {r}: uploads {t[0]:.4f} s  k_cg_rank {t[1]:.4f} s  '
+                f'k_cf_tables {t[2]:.4f} s  k_cf_sums {t[3]:.4f} s  '
+                f'k_cf_reduce {t[4]:.4f} s', flush=True)
+        total, f_up, f_rank, f_tab, f_sum, f_red = min(runs)
+        print(f'  fastest of {reps} (device events): pass {total:.4f} s; '
+            f'k_cf_sums reads {8 * seen / f_sum / 1e9:.1f} GB/s of tables, '
+            f'k_cg_accum {4 * steps / t_acc / 1e9:.1f} GB/s of trace; '
+            f'k_cf_sums / k_cg_accum time {f_sum / t_acc:.2f}x', flush=True)
+        t0 = time.perf_counter()
+        post.cell_fit(data, params, FN, FP, chunk, slab)
+        t0 = lap('Posterior.cell_fit (call, three vectors to the host)', t0)
     post.close()
     sys.exit(0)
 tree = post.ward()
