@@ -41,6 +41,7 @@ SUPPORT_KC = 128    # include/bnpc_hip.h: BNPC_SUPPORT_KC (clusters per pass)
 # bnpc_codist.hip, 8 ceil(N / 32) + 1040 bytes <= CG_LDS_MAX = 65536
 CELL_RANK_LDS_CELLS = 257984
 CELL_TILE = 8       # bnpc_codist.hip: CG_CELLS (cells per workgroup)
+MUT_FIT_ROWS = 32   # bnpc_codist.hip: MF_ROWS (cluster rows of a wave's LDS tile)
 
 _i64 = C.c_int64
 # array arguments travel as plain addresses (building a typed ctypes pointer
@@ -317,6 +318,11 @@ SIGNATURES = {
         _pd, _pd, _i64, _i64, _pd, _pd, _pd, _pd]),
     'bnpc_post_cell_fit_times': (C.c_int, [C.c_void_p, C.c_void_p, _pf, _i64,
         _i64, _pd, _pd, _i64, _i64, C.POINTER(C.c_float)]),
+    'bnpc_post_mutation_fit': (C.c_int, [C.c_void_p, C.c_void_p, _pf, _i64,
+        _i64, _pd, _pd, _pi32, _i64, _pd, _pd, _pd, _pd, _pd, _pi64, _pi64,
+        _pd]),
+    'bnpc_post_mutation_fit_times': (C.c_int, [C.c_void_p, C.c_void_p, _pf,
+        _i64, _i64, _pd, _pd, _pi32, _i64, C.POINTER(C.c_float)]),
     'bnpc_post_ward': (C.c_int, [C.c_void_p, _pd]),
     'bnpc_post_ward_stats': (C.c_int, [C.c_void_p, C.POINTER(_i64),
         C.POINTER(_i64)]),
@@ -861,6 +867,52 @@ class Posterior:
         check(load().bnpc_post_cell_fit_times(self._h, ptr(codes), ptr(par),
             par.shape[1], par.shape[2], ptr(FN), ptr(FP), int(chunk),
             int(slab), ms), 'post_cell_fit_times')
+        return tuple(x / 1e3 for x in ms)
+
+    def _order(self, order):
+        if order is None:
+            return None
+        order = np.ascontiguousarray(order, dtype=np.int32)
+        if order.shape != (self.N,):
+            raise ValueError(f'the order hint must hold {self.N} labels')
+        return order
+
+    def mutation_fit(self, data, params, FN, FP, order=None, chunk=0,
+            matrix=False):
+        """The fit of every mutation's column over the posterior samples and
+        the error rates it implies (bnpc_post_mutation_fit) -> (sum_ll,
+        sum_ll2, efn, efp, eg1, call1_obs1, call1_obs0, ll): (M,) arrays, five
+        float64 and two int64, as postproc.host_mutation_fit defines them,
+        and - with matrix=True, else None - the (S, M) matrix ll.  data,
+        params, FN, FP, chunk as for cell_fit.  order: N labels of any
+        clustering the samples mostly agree with (None: the last sample's);
+        the pass sorts the cells by it, which changes its speed and no bit of
+        its results."""
+        codes, par, FN, FP = self._fit_args(data, params, FN, FP)
+        order = self._order(order)
+        M = par.shape[2]
+        out = [np.empty(M) for _ in range(5)]
+        out += [np.empty(M, dtype=np.int64) for _ in range(2)]
+        ll = np.empty((self.S, M)) if matrix else None
+        check(load().bnpc_post_mutation_fit(self._h, ptr(codes), ptr(par),
+            par.shape[1], M, ptr(FN), ptr(FP),
+            None if order is None else ptr(order), int(chunk),
+            *[ptr(x) for x in out], None if ll is None else ptr(ll)),
+            'post_mutation_fit')
+        return tuple(out) + (ll,)
+
+    def mutation_fit_times(self, data, params, FN, FP, order=None, chunk=0):
+        """Seconds by device events, summed over one mutation_fit call that
+        brings nothing back: (uploads and mask kernel, rank kernel, counting
+        kernel, 0 - the subtotals are the counting kernel's tail -,
+        per-mutation reduction)."""
+        codes, par, FN, FP = self._fit_args(data, params, FN, FP)
+        order = self._order(order)
+        ms = (C.c_float * 5)()
+        check(load().bnpc_post_mutation_fit_times(self._h, ptr(codes),
+            ptr(par), par.shape[1], par.shape[2], ptr(FN), ptr(FP),
+            None if order is None else ptr(order), int(chunk), ms),
+            'post_mutation_fit_times')
         return tuple(x / 1e3 for x in ms)
 
     def close(self):

@@ -2476,3 +2476,474 @@ extern "C" int bnpc_post_cell_fit_times(bnpc_post *p, const uint8_t *codes,
     return cf_run(p, codes, params, W, M, FN, FP, chunk, slab, nullptr,
                   nullptr, nullptr, nullptr, ms);
 }
+
+// ---------------------------------------------------------------------------
+// Per-mutation posterior fit and error rates (-pm): how well the model
+// explains every column of the data, and the error rates the column implies.
+// Within one sample all cells of a cluster share their parameter row, so
+// everything per mutation follows from the exact column counts
+//   c1[s][r][m], c0[s][r][m] = cells of row r in sample s that show a 1 / a 0
+// and a float64 walk down the sample's rows.  With th = P[s][r][m] (float32),
+// t = (double)th, o = (double)(1.0f - th) and the expressions of k_cf_tables,
+//   a1 = t * (1 - FN[s])  b1 = o * FP[s]        d1 = a1 + b1  L1 = log(d1)
+//   a0 = t * FN[s]        b0 = o * (1 - FP[s])  d0 = a0 + b0  L0 = log(d0)
+//   qfp = b1 / d1   qfn = a0 / d0
+// per (s, m), over r = 0 .. D_s - 1 in increasing r from 0.0:
+//   ll  += (double)c1 * L1 + (double)c0 * L0      efn += (double)c0 * qfn
+//   efp += (double)c1 * qfp      eg1 += (double)c1 * (a1 / d1) + (double)c0 * qfn
+//   call1_obs1 += c1, call1_obs0 += c0 where th > 0.5f
+// and per mutation, over the samples in increasing s: the sums of ll, ll * ll,
+// efn, efp, eg1 and the two integers.  postproc.host_mutation_fit is the host
+// loop this is pinned to: everything but log bit for bit.
+//
+// The counts do not depend on the order of the cells, so once per call the
+// cells are sorted by a hint clustering and the data become 64-cell lane masks
+// {ones, zeros}[block of 64 cells][mutation] (k_mf_masks).  Per chunk of the
+// trace:
+// k_cg_rank   every cell's rank in the chunk's samples (as for -pg)
+// k_mf_count  wave = (sample, 64 mutations), lane = mutation.  Per block of
+//             cells the wave turns the block's 64 ranks (lane = cell for this
+//             one load) into wave-uniform (row, member mask) pairs - the first
+//             remaining lane's rank, the ballot of the equal ones, repeat -
+//             and per pair adds popcount(ones & mask), popcount(zeros & mask)
+//             to counts[row][lane] in LDS.  The wave owns its tile: no
+//             atomics, no barrier.  A tile holds MF_ROWS rows; a sample with
+//             more takes its rows in passes of MF_ROWS, the subtotals carried
+//             in registers, so the order over r is the same.  After a pass
+//             lane m walks the pass's rows and forms the subtotals of (s, m).
+// k_mf_reduce thread = mutation: the chunk's subtotals in sample order into
+//             the seven accumulators, which stay on the device between chunks.
+// ---------------------------------------------------------------------------
+#define MF_ROWS 32                  // rows of a wave's LDS tile: 16 KB
+
+// cells [0, cells) of a slab in sorted order, codes their [cells][M] bytes;
+// block b of the slab into masks[b][Mp] (x: ones, y: zeros; the cells past
+// `cells` and the columns past M empty).  bad: the smallest slab index of a
+// code other than 0 / 1 / 3.
+__global__ __launch_bounds__(256) void k_mf_masks(
+    const uint8_t *__restrict__ codes, long long cells, long long M,
+    long long Mp, ulonglong2 *__restrict__ masks,
+    unsigned long long *__restrict__ bad)
+{
+    const long long m = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (m >= Mp) return;
+    const long long j0 = (long long)blockIdx.y * 64;
+    unsigned long long ones = 0ull, zeros = 0ull;
+    if (m < M) {
+        const int n = (int)(cells - j0 < 64 ? cells - j0 : 64);
+        for (int l = 0; l < n; l++) {
+            const size_t at = (size_t)(j0 + l) * M + m;
+            const unsigned c = codes[at];
+            if (c == 1u)
+                ones |= 1ull << l;
+            else if (c == 0u)
+                zeros |= 1ull << l;
+            else if (c != 3u)
+                atomicMin(bad, (unsigned long long)at);
+        }
+    }
+    masks[(size_t)blockIdx.y * Mp + m] = make_ulonglong2(ones, zeros);
+}
+
+// one chunk of sc samples: P its [sc][W][M] trace, rank its [sc][N] rows by
+// cell, perm the cells in sorted order, masks the [nb][Mp] lane masks of the
+// sorted cells; sub the chunk's [6][sc][M] subtotals (ll, efn, efp, eg1 as
+// float64, call1_obs1, call1_obs0 as int64)
+__global__ __launch_bounds__(64) void k_mf_count(
+    const float *__restrict__ P, int sc, int W, long long M, long long Mp,
+    const int *__restrict__ distinct, const double *__restrict__ FN,
+    const double *__restrict__ FP, const unsigned short *__restrict__ rank,
+    const int *__restrict__ perm, long long N,
+    const ulonglong2 *__restrict__ masks, long long nb,
+    double *__restrict__ sub)
+{
+    __shared__ unsigned cnt[MF_ROWS][2][64];
+    const int lane = threadIdx.x;
+    const long long m = (long long)blockIdx.x * 64 + lane;
+    const bool mv = m < M;
+    const ulonglong2 *mk_col = masks + m;           // m < Mp always
+    const size_t plane = (size_t)sc * M;
+    for (int q = blockIdx.y; q < sc; q += gridDim.y) {
+        const int D = distinct[q];
+        const double fn = FN[q], fp = FP[q];
+        const unsigned short *rk = rank + (size_t)q * N;
+        const float *Pq = P + (size_t)q * W * M + (mv ? m : 0);
+        double ll = 0.0, efn = 0.0, efp = 0.0, eg1 = 0.0;
+        long long k1 = 0, k0 = 0;
+        for (int r0 = 0; r0 < D; r0 += MF_ROWS) {
+            const int rows = D - r0 < MF_ROWS ? D - r0 : MF_ROWS;
+            for (int r = 0; r < rows; r++) {
+                cnt[r][0][lane] = 0u;
+                cnt[r][1][lane] = 0u;
+            }
+            for (long long b = 0; b < nb; b++) {
+                // lane = cell of the block here
+                const long long j = b * 64 + lane;
+                const bool in = j < N;
+                const int mine = in ? (int)rk[perm[j]] : -1;
+                const ulonglong2 w = mk_col[(size_t)b * Mp];
+                unsigned long long left = __ballot(in);
+                while (left) {
+                    const int first = __ffsll((unsigned long long)left) - 1;
+                    const int r = __builtin_amdgcn_readlane(mine, first);
+                    const unsigned long long members = __ballot(mine == r);
+                    left &= ~members;
+                    const int at = r - r0;
+                    if (at >= 0 && at < rows) {     // the same in every lane
+                        cnt[at][0][lane] += (unsigned)__popcll(w.x & members);
+                        cnt[at][1][lane] += (unsigned)__popcll(w.y & members);
+                    }
+                }
+            }
+            // lane = mutation: the pass's rows in increasing r
+            for (int r = 0; r < rows; r++) {
+                const unsigned u1 = cnt[r][0][lane], u0 = cnt[r][1][lane];
+                const float th = mv ? Pq[(size_t)(r0 + r) * M] : 0.5f;
+                const double t = (double)th;
+                const double o = (double)(1.0f - th);
+                const double a1 = t * (1.0 - fn), b1 = o * fp;
+                const double a0 = t * fn, b0 = o * (1.0 - fp);
+                const double d1 = a1 + b1, d0 = a0 + b0;
+                const double qfp = b1 / d1, qfn = a0 / d0;
+                const double c1 = (double)u1, c0 = (double)u0;
+                ll += c1 * log(d1) + c0 * log(d0);
+                efn += c0 * qfn;
+                efp += c1 * qfp;
+                eg1 += c1 * (a1 / d1) + c0 * qfn;
+                if (th > 0.5f) {
+                    k1 += u1;
+                    k0 += u0;
+                }
+            }
+        }
+        if (mv) {
+            const size_t at = (size_t)q * M + m;
+            sub[at] = ll;
+            sub[plane + at] = efn;
+            sub[2 * plane + at] = efp;
+            sub[3 * plane + at] = eg1;
+            ((long long *)sub)[4 * plane + at] = k1;
+            ((long long *)sub)[5 * plane + at] = k0;
+        }
+    }
+}
+
+// mutation m: the chunk's sc subtotals in sample order into acc, [7][M]:
+// sum_ll, sum_ll2, efn, efp, eg1 (float64), call1_obs1, call1_obs0 (int64)
+__global__ __launch_bounds__(256) void k_mf_reduce(
+    const double *__restrict__ sub, int sc, long long M,
+    double *__restrict__ acc)
+{
+    const long long m = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (m >= M) return;
+    const size_t plane = (size_t)sc * M;
+    const long long *isub = (const long long *)sub;
+    long long *iacc = (long long *)acc;
+    double s1 = acc[m], s2 = acc[M + m], fn = acc[2 * M + m];
+    double fp = acc[3 * M + m], g1 = acc[4 * M + m];
+    long long k1 = iacc[5 * M + m], k0 = iacc[6 * M + m];
+    for (int q = 0; q < sc; q++) {
+        const size_t at = (size_t)q * M + m;
+        const double v = sub[at];
+        s1 += v;
+        s2 += v * v;
+        fn += sub[plane + at];
+        fp += sub[2 * plane + at];
+        g1 += sub[3 * plane + at];
+        k1 += isub[4 * plane + at];
+        k0 += isub[5 * plane + at];
+    }
+    acc[m] = s1;
+    acc[M + m] = s2;
+    acc[2 * M + m] = fn;
+    acc[3 * M + m] = fp;
+    acc[4 * M + m] = g1;
+    iacc[5 * M + m] = k1;
+    iacc[6 * M + m] = k0;
+}
+
+// ms (NULL, or 5 floats): device-event milliseconds summed over the call -
+// ms[0] the uploads (data, permutation, trace) and k_mf_masks, ms[1]
+// k_cg_rank, ms[2] k_mf_count, ms[3] 0 (the subtotals are the tail of
+// k_mf_count), ms[4] k_mf_reduce
+static int mf_run(bnpc_post *p, const uint8_t *codes, const float *params,
+                  int64_t W, int64_t M, const double *FN, const double *FP,
+                  const int32_t *order_hint, int64_t chunk, double *const out[5],
+                  int64_t *const iout[2], double *ll, float *ms)
+{
+    if (!p || !codes || !params || !FN || !FP || W < 1
+        || W >= (int64_t)GT_MIXED || M < 1
+        || (W * M + 255) / 256 > (int64_t)INT_MAX || chunk < 0) {
+        bnpc_set_error("bad argument: the mutation fit needs the data's codes, "
+                       "a 1 <= W < 65534 x M >= 1 trace, FN, FP and chunk >= 0");
+        return 2;
+    }
+    if (!p->assign || !p->labels_in_range) {
+        bnpc_set_error("mutation fit: the sample labels must lie in [0, N = "
+                       "%lld)", (long long)p->N);
+        return 2;
+    }
+    const int64_t S = p->S, N = p->N;
+    for (int64_t s = 0; s < S; s++) {
+        if (!(FN[s] > 0.0 && FN[s] < 1.0 && FP[s] > 0.0 && FP[s] < 1.0)) {
+            bnpc_set_error("mutation fit: FN = %g, FP = %g of sample %lld are "
+                           "not both inside (0, 1)", FN[s], FP[s],
+                           (long long)s);
+            return 2;
+        }
+    }
+    PCK(hipSetDevice(p->device));
+    GtBuffers buf;
+    CgEvents evs;
+    auto oom = [](hipError_t e) {
+        (void)hipGetLastError();
+        bnpc_set_error("mutation fit: out of device memory (%s)",
+                       hipGetErrorString(e));
+        return 5;
+    };
+#define MFA(expr)                                                            \
+    do {                                                                     \
+        hipError_t a_ = (expr);                                              \
+        if (a_ == hipErrorOutOfMemory) return oom(a_);                       \
+        PCK(a_);                                                             \
+    } while (0)
+
+    // every sample's cluster count against the trace's rows, before anything
+    // is added up; the counting kernel reads the counts too
+    GtArea area;
+    int *d_distinct;
+    MFA(buf.alloc(&d_distinct, S));
+    if ((size_t)cg_rank_words(N) * 4 <= CG_LDS_MAX) {
+        area.grid = (unsigned)std::min<int64_t>(S, 65535);
+        area.lds = (size_t)cg_rank_words(N) * 4;
+    } else {
+        area.grid = (unsigned)std::min<int64_t>(S, GT_GLOBAL_WG);
+        area.stride = cg_rank_words(N);
+        MFA(buf.alloc(&area.scratch, (size_t)area.grid * area.stride));
+    }
+    std::vector<int> distinct(S);
+    for (int64_t s0 = 0; s0 < S; s0 += INT_MAX) {
+        const int64_t n = std::min<int64_t>(INT_MAX, S - s0);
+        hipLaunchKernelGGL(k_cg_rank, dim3(area.grid), dim3(256), area.lds, 0,
+                           p->assign, (long long)s0, (int)n, (long long)N, 0LL,
+                           0LL, 0LL, area.scratch, area.stride,
+                           (unsigned short *)nullptr, d_distinct + s0);
+        PCK(hipGetLastError());
+    }
+    PCK(hipMemcpy(distinct.data(), d_distinct, S * sizeof(int),
+                  hipMemcpyDeviceToHost));
+    for (int64_t s = 0; s < S; s++) {
+        if (distinct[s] > W) {
+            bnpc_set_error("mutation fit: sample %lld has %d clusters, the "
+                           "trace %lld rows", (long long)s, distinct[s],
+                           (long long)W);
+            return 2;
+        }
+    }
+
+    // the cells in the order of the hint's labels (stable): the labels of the
+    // last sample where there is no hint
+    std::vector<int32_t> hint(N);
+    if (order_hint)
+        memcpy(hint.data(), order_hint, (size_t)N * sizeof(int32_t));
+    else
+        PCK(hipMemcpy(hint.data(), p->assign + (size_t)(S - 1) * N,
+                      (size_t)N * sizeof(int32_t), hipMemcpyDeviceToHost));
+    std::vector<int> perm(N);
+    for (int64_t i = 0; i < N; i++) perm[i] = (int)i;
+    std::stable_sort(perm.begin(), perm.end(),
+                     [&](int a, int b) { return hint[a] < hint[b]; });
+
+    // the working set: the lane masks, a slab of the data while they are
+    // built, the chunk of the trace with its ranks and subtotals
+    const int64_t nb = (N + 63) / 64;
+    const int64_t Mp = (M + 63) / 64 * 64;
+    const size_t sample_floats = (size_t)W * M;
+    const size_t per_sample = sample_floats * 4 + (size_t)M * 48 + (size_t)N * 2;
+    int64_t sc = chunk;
+    if (sc == 0)
+        sc = std::max<int64_t>(1, (int64_t)(((size_t)512 << 20) / per_sample));
+    sc = std::min<int64_t>(std::min(sc, S), INT_MAX);
+    // (64 cells at the least, about 64 MB of codes and what a launch's second
+    // dimension takes at the most)
+    const int64_t slab_blocks = std::min<int64_t>(std::min<int64_t>(nb, 65535),
+        std::max<int64_t>(1, (int64_t)(((size_t)64 << 20) / ((size_t)M * 64))));
+    const int64_t slab_cells = slab_blocks * 64;
+    const size_t need = (size_t)nb * Mp * 16 + (size_t)slab_cells * M
+        + (size_t)sc * per_sample + (size_t)M * 56 + (size_t)N * 4
+        + (size_t)S * 16;
+    size_t free_b = 0, total_b = 0;
+    PCK(hipMemGetInfo(&free_b, &total_b));
+    if (need + ((size_t)64 << 20) > free_b) {
+        bnpc_set_error("mutation fit: %lld cells x %lld mutations with chunks "
+                       "of %lld samples need %.1f GB, %.1f GB of device memory "
+                       "are free", (long long)N, (long long)M, (long long)sc,
+                       need / 1e9, free_b / 1e9);
+        return 5;
+    }
+    ulonglong2 *d_masks;
+    uint8_t *d_codes;
+    unsigned long long *d_bad;
+    int *d_perm;
+    float *d_P;
+    unsigned short *d_rank;
+    double *d_sub, *d_acc, *d_FN, *d_FP;
+    MFA(buf.alloc(&d_masks, (size_t)nb * Mp));
+    MFA(buf.alloc(&d_codes, (size_t)slab_cells * M));
+    MFA(buf.alloc(&d_bad, 1));
+    MFA(buf.alloc(&d_perm, (size_t)N));
+    MFA(buf.alloc(&d_P, (size_t)sc * sample_floats));
+    MFA(buf.alloc(&d_rank, (size_t)sc * N));
+    MFA(buf.alloc(&d_sub, (size_t)6 * sc * M));
+    MFA(buf.alloc(&d_acc, (size_t)7 * M));
+    MFA(buf.alloc(&d_FN, (size_t)S));
+    MFA(buf.alloc(&d_FP, (size_t)S));
+#undef MFA
+    if (ms) {
+        for (int k = 0; k < 5; k++) ms[k] = 0.0f;
+        PCK(hipEventCreate(&evs.ev[0]));
+        PCK(hipEventCreate(&evs.ev[1]));
+    }
+    // a lap of the device's clock: begin(), the work, end(its slot of ms)
+    int lap_rc = 0;
+    auto begin = [&]() {
+        if (ms && hipEventRecord(evs.ev[0], 0) != hipSuccess) lap_rc = 1;
+    };
+    auto end = [&](int which) {
+        if (!ms) return;
+        float t = 0.0f;
+        if (hipEventRecord(evs.ev[1], 0) != hipSuccess
+            || hipEventSynchronize(evs.ev[1]) != hipSuccess
+            || hipEventElapsedTime(&t, evs.ev[0], evs.ev[1]) != hipSuccess)
+            lap_rc = 1;
+        ms[which] += t;
+    };
+
+    // the lane masks, a slab of sorted cells at a time
+    PCK(hipMemset(d_bad, 0xff, sizeof(unsigned long long)));
+    PCK(hipMemset(d_acc, 0, (size_t)7 * M * sizeof(double)));
+    PCK(hipMemcpy(d_FN, FN, S * sizeof(double), hipMemcpyHostToDevice));
+    PCK(hipMemcpy(d_FP, FP, S * sizeof(double), hipMemcpyHostToDevice));
+    std::vector<uint8_t> stage((size_t)std::min(slab_cells, N) * M);
+    for (int64_t j0 = 0; j0 < N; j0 += slab_cells) {
+        const int64_t cells = std::min(slab_cells, N - j0);
+        for (int64_t j = 0; j < cells; j++)
+            memcpy(stage.data() + (size_t)j * M,
+                   codes + (size_t)perm[j0 + j] * M, (size_t)M);
+        begin();
+        PCK(hipMemcpy(d_codes, stage.data(), (size_t)cells * M,
+                      hipMemcpyHostToDevice));
+        hipLaunchKernelGGL(k_mf_masks,
+                           dim3((unsigned)((Mp + 255) / 256),
+                                (unsigned)((cells + 63) / 64)),
+                           dim3(256), 0, 0, d_codes, (long long)cells,
+                           (long long)M, (long long)Mp,
+                           d_masks + (size_t)(j0 / 64) * Mp, d_bad);
+        PCK(hipGetLastError());
+        end(0);
+        unsigned long long bad = 0;
+        PCK(hipMemcpy(&bad, d_bad, sizeof(bad), hipMemcpyDeviceToHost));
+        if (bad != ~0ull) {
+            const int64_t j = j0 + (int64_t)(bad / (unsigned long long)M);
+            const int64_t m = (int64_t)(bad % (unsigned long long)M);
+            bnpc_set_error("mutation fit: code %d of cell %lld at mutation "
+                           "%lld is not 0, 1 or 3",
+                           (int)codes[(size_t)perm[j] * M + m],
+                           (long long)perm[j], (long long)m);
+            return 2;
+        }
+    }
+    begin();
+    PCK(hipMemcpy(d_perm, perm.data(), (size_t)N * sizeof(int),
+                  hipMemcpyHostToDevice));
+    end(0);
+
+    const unsigned mtiles = (unsigned)(Mp / 64);
+    for (int64_t s0 = 0; s0 < S; s0 += sc) {
+        const int64_t n = std::min(sc, S - s0);
+        begin();
+        PCK(hipMemcpy(d_P, params + (size_t)s0 * sample_floats,
+                      (size_t)n * sample_floats * sizeof(float),
+                      hipMemcpyHostToDevice));
+        end(0);
+        begin();
+        hipLaunchKernelGGL(k_cg_rank,
+                           dim3((unsigned)std::min<int64_t>(n, area.grid)),
+                           dim3(256), area.lds, 0, p->assign, (long long)s0,
+                           (int)n, (long long)N, 0LL, (long long)N,
+                           (long long)N, area.scratch, area.stride, d_rank,
+                           (int *)nullptr);
+        PCK(hipGetLastError());
+        end(1);
+        begin();
+        hipLaunchKernelGGL(k_mf_count,
+                           dim3(mtiles, (unsigned)std::min<int64_t>(n, 65535)),
+                           dim3(64), 0, 0, d_P, (int)n, (int)W, (long long)M,
+                           (long long)Mp, d_distinct + s0, d_FN + s0,
+                           d_FP + s0, d_rank, d_perm, (long long)N, d_masks,
+                           (long long)nb, d_sub);
+        PCK(hipGetLastError());
+        end(2);
+        begin();
+        hipLaunchKernelGGL(k_mf_reduce, dim3((unsigned)((M + 255) / 256)),
+                           dim3(256), 0, 0, d_sub, (int)n, (long long)M,
+                           d_acc);
+        PCK(hipGetLastError());
+        end(4);
+        // (the chunk's ll: the first plane of its subtotals; a failure here
+        // is a device failure, not an argument's)
+        if (ll)
+            PCK(hipMemcpy(ll + (size_t)s0 * M, d_sub,
+                          (size_t)n * M * sizeof(double),
+                          hipMemcpyDeviceToHost));
+    }
+    PCK(hipDeviceSynchronize());
+    for (int k = 0; k < 5; k++)
+        if (out[k])
+            PCK(hipMemcpy(out[k], d_acc + (size_t)k * M, M * sizeof(double),
+                          hipMemcpyDeviceToHost));
+    for (int k = 0; k < 2; k++)
+        if (iout[k])
+            PCK(hipMemcpy(iout[k], d_acc + (size_t)(5 + k) * M,
+                          M * sizeof(int64_t), hipMemcpyDeviceToHost));
+    if (lap_rc) {
+        bnpc_set_error("mutation fit: the device events failed");
+        return 1;
+    }
+    return 0;
+}
+
+extern "C" int bnpc_post_mutation_fit(bnpc_post *p, const uint8_t *codes,
+                                      const float *params, int64_t W,
+                                      int64_t M, const double *FN,
+                                      const double *FP,
+                                      const int32_t *order_hint, int64_t chunk,
+                                      double *sum_ll, double *sum_ll2,
+                                      double *efn, double *efp, double *eg1,
+                                      int64_t *call1_obs1, int64_t *call1_obs0,
+                                      double *ll)
+{
+    double *const out[5] = {sum_ll, sum_ll2, efn, efp, eg1};
+    int64_t *const iout[2] = {call1_obs1, call1_obs0};
+    return mf_run(p, codes, params, W, M, FN, FP, order_hint, chunk, out, iout,
+                  ll, nullptr);
+}
+
+// diagnostic (tools/posterior_bench.py): one bnpc_post_mutation_fit call
+// without its results' way back, by device events (see mf_run)
+extern "C" int bnpc_post_mutation_fit_times(bnpc_post *p, const uint8_t *codes,
+                                            const float *params, int64_t W,
+                                            int64_t M, const double *FN,
+                                            const double *FP,
+                                            const int32_t *order_hint,
+                                            int64_t chunk, float *ms)
+{
+    if (!ms) {
+        bnpc_set_error("bad argument: NULL");
+        return 2;
+    }
+    double *const out[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    int64_t *const iout[2] = {nullptr, nullptr};
+    return mf_run(p, codes, params, W, M, FN, FP, order_hint, chunk, out, iout,
+                  nullptr, ms);
+}

@@ -366,6 +366,58 @@ def save_cell_fit(out_dir, chain, est, fit, assignment, names=None):
     return paths
 
 
+def save_mutation_fit(out_dir, chain, est, fit, names=None):
+    """The -pm files of postproc.mutation_fit for one (chain, estimator) row.
+    mutation_fit_<est>_<chain>.tsv: per mutation its name (`names`, the
+    loader's mutation names, when there is one per mutation, else 0..M-1) and
+    the columns of postproc.MUTATION_FIT_COLUMNS: integers plain, floats
+    %.4f, FP_model and FP_call %.8f (as errors.txt).
+    mutation_summary_<est>_<chain>.txt: `key: value` lines - samples,
+    mutations, observations, the pooled FN_model, FP_model, FN_call, FP_call,
+    the posterior means FN and FP of the run's own rates, worst_mutations
+    (the ten with the smallest mean log-likelihood per observed entry among
+    those with observations) and highest_FN (the ten with the largest
+    FN_model among those with at least one expected carrier per sample), as
+    name:value pairs."""
+    from bnpc_amd.postproc import MUTATION_FIT_COLUMNS as columns
+    M = fit['n_obs'].size
+    index = np.arange(M)
+    if names is not None and np.asarray(names).size == M:
+        index = np.asarray(names)
+    index = index.tolist()
+    tag = f'{chain:0>2}'
+    paths = [os.path.join(out_dir, f'mutation_fit_{est}_{tag}.tsv'),
+        os.path.join(out_dir, f'mutation_summary_{est}_{tag}.txt')]
+    fine = ('FP_model', 'FP_call')
+
+    def cell(key, val):
+        if key.startswith('n_'):
+            return str(int(val))
+        return f'{val:.8f}' if key in fine else f'{val:.4f}'
+    with open(paths[0], 'w') as f:
+        f.write('mutation\t' + '\t'.join(columns) + '\n')
+        for m, name in enumerate(index):
+            f.write(f'{name}\t'
+                + '\t'.join(cell(k, fit[k][m]) for k in columns) + '\n')
+    total = fit['total']
+    per_obs = fit['mean_ll_per_obs']
+    seen = np.flatnonzero(fit['n_obs'] > 0)
+    worst = seen[np.argsort(per_obs[seen], kind='stable')[:10]]
+    carried = np.flatnonzero(fit['eg1'] / total['samples'] >= 1)
+    high = carried[np.argsort(-fit['FN_model'][carried], kind='stable')[:10]]
+    with open(paths[1], 'w') as f:
+        for key in ('samples', 'mutations', 'observations'):
+            f.write(f'{key}: {total[key]}\n')
+        for key in ('FN_model', 'FP_model', 'FN_call', 'FP_call', 'FN', 'FP'):
+            f.write(f'{key}: {cell(key, total[key])}\n')
+        f.write('worst_mutations: ' + ' '.join(f'{index[m]}:{per_obs[m]:.4f}'
+            for m in worst.tolist()) + '\n')
+        f.write('highest_FN: ' + ' '.join(
+            f'{index[m]}:{fit["FN_model"][m]:.4f}' for m in high.tolist())
+            + '\n')
+    return paths
+
+
 def save_metric(path, column, rows):
     """V_measure.txt / ARI.txt / hammingDist.txt (dpmmIO.py:514-542): a
     tab-separated `chain  estimator  <column>` table, floats as to_csv

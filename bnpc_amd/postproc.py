@@ -24,6 +24,9 @@ The -pf tables (per-cell posterior fit and the run's WAIC, from the pointwise
 log-likelihood of every cell in every sample - not a reference output) are a
 device pass over the samples, the parameter trace and the data
 (bnpc_post_cell_fit; host_cell_fit is the host loop it is pinned to).
+The -pm tables (per-mutation posterior fit and the error rates every column
+implies - not a reference output) are a device pass over the same inputs
+(bnpc_post_mutation_fit; host_mutation_fit is the host loop it is pinned to).
 The -tc / -td metrics (V-measure, ARI, Hamming; utils.py:49-72) are
 restated from integer counts at the end; tree helpers are out of scope.
 """
@@ -388,7 +391,8 @@ def concat_chain_results(results):
     return pooled
 
 
-def posterior_estimate(results, data, support=False, cells=False, fit=False):
+def posterior_estimate(results, data, support=False, cells=False, fit=False,
+        mutations=False):
     """`-e posterior` (the default estimator), chains pooled
     (utils.py:195-244).  support=True: the key 'support' holds the tables of
     cluster_support for the MPEAR clustering, made from the pair counts of
@@ -396,10 +400,12 @@ def posterior_estimate(results, data, support=False, cells=False, fit=False):
     key 'cell_genotypes' holds the tables of cell_genotypes, made from the
     samples the same handle keeps on the device.  fit=True: the key 'fit'
     holds the tables of cell_fit, from the same samples, the data and the
-    samples' error rates."""
+    samples' error rates.  mutations=True: the key 'mutation_fit' holds the
+    tables of mutation_fit, from the same inputs, the cells sorted by the
+    MPEAR clustering."""
     res = concat_chain_results(results)
     tables = {}
-    if support or cells or fit:
+    if support or cells or fit or mutations:
         def while_open(post, assign):
             if support:
                 tables['support'] = posterior_support(post, assign)
@@ -409,6 +415,10 @@ def posterior_estimate(results, data, support=False, cells=False, fit=False):
             if fit:
                 tables['fit'] = cell_fit(post, data, res['assignments'],
                     res['params'], res['FN'], res['FP'])
+            if mutations:
+                tables['mutation_fit'] = mutation_fit(post, data,
+                    res['assignments'], res['params'], res['FN'], res['FP'],
+                    order=assign)
     else:
         while_open = None
     assign, params = _mean_hierarchy(res['assignments'], res['params'],
@@ -653,6 +663,164 @@ def cell_fit(post, data, assignments, params_full, FN, FP):
         'total': {'samples': int(S), 'cells': int(N),
             'observations': int(n_obs.sum()), 'lppd': lppd, 'p_waic': p_waic,
             'waic': -2 * (lppd - p_waic)}}
+
+
+# ---------------------------------------------------------------------------
+# per-mutation posterior fit and error rates (-pm): how well the model
+# explains every column, and the error rates the column implies; not a
+# reference output, so the arithmetic and the summation order below are the
+# specification
+# ---------------------------------------------------------------------------
+def host_mutation_fit(data, assignments, params_full, FN, FP):
+    """The log-likelihood of every mutation's column in every posterior
+    sample, the error rates the fitted model implies for it, and their
+    reductions over the samples; the plain loop bnpc_post_mutation_fit is
+    pinned to.  Inputs as host_cell_fit.  All cells of a cluster share their
+    parameter row, so per sample s, row r and mutation m everything follows
+    from c1, c0 - the row's cells that show a 1 / a 0 at m - and, with
+    th = float32 params_full[s][r][m], t = float64(th) and
+    o = float64(float32(1) - th),
+      a1 = t * (1 - FN[s])  b1 = o * FP[s]        d1 = a1 + b1  L1 = log(d1)
+      a0 = t * FN[s]        b0 = o * (1 - FP[s])  d0 = a0 + b0  L0 = log(d0)
+      qfp = b1 / d1     an observed 1 is a false positive
+      qfn = a0 / d0     an observed 0 is a false negative
+    (host_cell_fit's expressions, each operation rounded on its own).  Per
+    (s, m), over the rows in increasing r from 0.0:
+      ll[s][m] = sum of c1 * L1 + c0 * L0      efn_s = sum of c0 * qfn
+      efp_s = sum of c1 * qfp      eg1_s = sum of c1 * (a1 / d1) + c0 * qfn
+    (eg1: the expected number of observed cells that carry the mutation), and
+    per mutation over the samples in increasing s from 0.0: sum_ll, sum_ll2
+    (of ll * ll), efn, efp, eg1; call1_obs1, call1_obs0 add c1 and c0 of the
+    rows with th > 0.5 (the rounding of host_cell_genotypes); n1, n0 count
+    the column's ones and zeros.
+    -> {'ll': (S, M) float64, 'sum_ll', 'sum_ll2', 'efn', 'efp', 'eg1': (M,)
+    float64, 'call1_obs1', 'call1_obs0', 'n1', 'n0': (M,) int64}"""
+    codes = data_codes(data)
+    assignments = np.asarray(assignments)
+    S = assignments.shape[0]
+    M = codes.shape[1]
+    FN = np.asarray(FN, dtype=np.float64)
+    FP = np.asarray(FP, dtype=np.float64)
+    is1, is0 = codes == 1, codes == 0
+    ll = np.empty((S, M))
+    sub = np.empty((3, S, M))
+    call = np.zeros((2, M), dtype=np.int64)
+    for s in range(S):
+        rank = np.unique(assignments[s], return_inverse=True)[1].ravel()
+        acc = np.zeros((4, M))
+        for r in range(rank.max() + 1):
+            member = rank == r
+            k1 = is1[member].sum(axis=0, dtype=np.int64)
+            k0 = is0[member].sum(axis=0, dtype=np.int64)
+            c1, c0 = k1.astype(np.float64), k0.astype(np.float64)
+            th = np.asarray(params_full[s][r], dtype=np.float32)
+            t = th.astype(np.float64)
+            o = (np.float32(1) - th).astype(np.float64)
+            a1, b1 = t * (1 - FN[s]), o * FP[s]
+            a0, b0 = t * FN[s], o * (1 - FP[s])
+            d1, d0 = a1 + b1, a0 + b0
+            qfp, qfn = b1 / d1, a0 / d0
+            acc[0] += c1 * np.log(d1) + c0 * np.log(d0)
+            acc[1] += c0 * qfn
+            acc[2] += c1 * qfp
+            acc[3] += c1 * (a1 / d1) + c0 * qfn
+            called = th > 0.5
+            call[0] += np.where(called, k1, 0)
+            call[1] += np.where(called, k0, 0)
+        ll[s] = acc[0]
+        sub[:, s] = acc[1:]
+    out = {'ll': ll, **mutation_fit_sums(ll)}
+    for k, key in enumerate(('efn', 'efp', 'eg1')):
+        out[key] = np.zeros(M)
+        for s in range(S):
+            out[key] += sub[k, s]
+    out.update(call1_obs1=call[0], call1_obs0=call[1],
+        n1=is1.sum(axis=0, dtype=np.int64), n0=is0.sum(axis=0, dtype=np.int64))
+    return out
+
+
+def mutation_fit_sums(ll):
+    """host_mutation_fit's reductions of an (S, M) matrix ll over the samples,
+    one sample at a time in increasing s from 0.0: {'sum_ll', 'sum_ll2'}."""
+    sum_ll, sum_ll2 = np.zeros(ll.shape[1]), np.zeros(ll.shape[1])
+    for row in ll:
+        sum_ll += row
+        sum_ll2 += row * row
+    return {'sum_ll': sum_ll, 'sum_ll2': sum_ll2}
+
+
+def _rate(num, den):
+    """num / den as float64, nan where den is 0 (arrays or scalars)."""
+    num = np.asarray(num, dtype=np.float64)
+    den = np.asarray(den, dtype=np.float64)
+    out = np.full(np.broadcast(num, den).shape, np.nan)
+    np.divide(num, den, out=out, where=den != 0)
+    return out if out.ndim else float(out)
+
+
+MUTATION_FIT_COLUMNS = ('n_obs', 'n_ones', 'n_zeros', 'mean_ll', 'sd_ll',
+    'mean_ll_per_obs', 'prevalence', 'FN_model', 'FP_model', 'FN_call',
+    'FP_call')
+
+
+def mutation_fit(post, data, assignments, params_full, FN, FP, order=None):
+    """The -pm tables: how well the model explains every mutation, and the
+    error rates its column implies, where the model has one global pair.  Per
+    mutation, (M,) arrays (MUTATION_FIT_COLUMNS): 'n_obs', 'n_ones',
+    'n_zeros' of the column; 'mean_ll' and 'sd_ll' (the sample standard
+    deviation; 0 for S = 1) of the column's log-likelihood over the samples,
+    'mean_ll_per_obs' (0 without observations); 'prevalence', the expected
+    share of the observed cells that carry the mutation (eg1 / (S n_obs));
+    'FN_model' = efn / eg1 and 'FP_model' = efp / (S n_obs - eg1), the rates
+    the fitted model implies - expected false negatives per expected carrier,
+    expected false positives per expected non-carrier; 'FN_call' =
+    call1_obs0 / (call1_obs1 + call1_obs0) and 'FP_call' = (S n1 -
+    call1_obs1) / (S n_obs - call1_obs1 - call1_obs0), the per-column,
+    posterior-averaged form of FN_data / FP_data of errors.txt, from the
+    genotypes called at th > 0.5.  A rate is nan where its denominator is 0.
+    'eg1' is the sum itself.  'total': {'samples', 'mutations',
+    'observations', the four rates pooled from the column sums, 'FN', 'FP':
+    the posterior means of the run's own rates}.  From an open clustering
+    handle: the device pass (Posterior.mutation_fit, the cells sorted by
+    `order`, any clustering's labels) where the handle has one, else the host
+    loop (host_mutation_fit); the same arithmetic on the sums either way."""
+    codes = data_codes(data)
+    n1 = (codes == 1).sum(axis=0, dtype=np.int64)
+    n0 = (codes == 0).sum(axis=0, dtype=np.int64)
+    device = getattr(post, 'mutation_fit', None)
+    if device is not None:
+        sum_ll, sum_ll2, efn, efp, eg1, c11, c10, _ = device(codes,
+            params_full, FN, FP, order=order)
+    else:
+        fit = host_mutation_fit(codes, assignments, params_full, FN, FP)
+        sum_ll, sum_ll2, efn, efp, eg1, c11, c10 = (fit[k] for k in (
+            'sum_ll', 'sum_ll2', 'efn', 'efp', 'eg1', 'call1_obs1',
+            'call1_obs0'))
+    S = int(np.asarray(assignments).shape[0])
+    M = n1.size
+    n_obs = n1 + n0
+    mean = sum_ll / S
+    sd = np.zeros(M)
+    if S > 1:
+        sd = np.sqrt(np.maximum(sum_ll2 / S - mean ** 2, 0) * S / (S - 1))
+    per_obs = np.zeros(M)
+    np.divide(mean, n_obs, out=per_obs, where=n_obs > 0)
+
+    def rates(n_obs, n1, efn, efp, eg1, c11, c10):
+        return {'FN_model': _rate(efn, eg1),
+            'FP_model': _rate(efp, S * n_obs - eg1),
+            'FN_call': _rate(c10, c11 + c10),
+            'FP_call': _rate(S * n1 - c11, S * n_obs - c11 - c10)}
+    total = {'samples': S, 'mutations': int(M),
+        'observations': int(n_obs.sum()),
+        **rates(int(n_obs.sum()), int(n1.sum()), efn.sum(), efp.sum(),
+            eg1.sum(), int(c11.sum()), int(c10.sum())),
+        'FN': float(np.mean(FN)), 'FP': float(np.mean(FP))}
+    return {'n_obs': n_obs, 'n_ones': n1, 'n_zeros': n0, 'mean_ll': mean,
+        'sd_ll': sd, 'mean_ll_per_obs': per_obs,
+        'prevalence': _rate(eg1, S * n_obs),
+        **rates(n_obs, n1, efn, efp, eg1, c11, c10), 'eg1': eg1,
+        'total': total}
 
 
 # ---------------------------------------------------------------------------

@@ -1110,6 +1110,53 @@ int bnpc_post_cell_fit_times(bnpc_post *post, const uint8_t *codes,
                              const float *params, int64_t W, int64_t M,
                              const double *FN, const double *FP,
                              int64_t chunk, int64_t slab, float *ms);
+/* Per-mutation posterior fit and error rates (-pm; not a reference output):
+ * how well the model explains every column of the data and the error rates
+ * the column implies.  With c1, c0 the cells of row r in sample s that show a
+ * 1 / a 0 at mutation m (exact integers), th = params[s][r][m], t = (double)th,
+ * o = (double)(1.0f - th) and
+ *   a1 = t * (1 - FN[s]), b1 = o * FP[s], d1 = a1 + b1, L1 = log(d1)
+ *   a0 = t * FN[s], b0 = o * (1 - FP[s]), d0 = a0 + b0, L0 = log(d0)
+ *   qfp = b1 / d1, qfn = a0 / d0
+ * (bnpc_post_cell_fit's expressions, every operation rounded on its own), per
+ * (s, m) over the sample's rows in increasing r from 0.0:
+ *   ll[s][m]  sum of (double)c1 * L1 + (double)c0 * L0
+ *   efn_s, efp_s, eg1_s  sums of (double)c0 * qfn, of (double)c1 * qfp and of
+ *             (double)c1 * (a1 / d1) + (double)c0 * qfn
+ * and per mutation, one sample at a time in increasing s from 0:
+ *   sum_ll, sum_ll2  the sums of ll[s][m] and of ll[s][m] * ll[s][m]
+ *   efn, efp, eg1    the sums of the subtotals
+ *   call1_obs1, call1_obs0  the sums of c1 and of c0 over the rows with
+ *             th > 0.5f: exact
+ * efn, efp, eg1 are bit for bit those of bnpc_amd.postproc.host_mutation_fit,
+ * sum_ll and sum_ll2 what its reductions make of the returned ll, and ll
+ * differs from the host's by the device's log alone.  Every output has the
+ * same bits for any chunk and any order_hint, on every call.  order_hint (N
+ * labels, or NULL: the last sample's) only sorts the cells, so that a block
+ * of 64 holds few clusters; params, W, chunk and the return codes as for
+ * bnpc_post_cell_fit (2, and no output written, for sample labels out of
+ * range, a sample with more clusters than W, an FN[s] or FP[s] not strictly
+ * inside (0, 1) or a code other than 0 / 1 / 3; 5 if the lane masks and a
+ * chunk do not fit the device's free memory).  The seven vectors (M each) and
+ * ll (S x M) may each be NULL. */
+int bnpc_post_mutation_fit(bnpc_post *post, const uint8_t *codes /* N x M: 0|1|3 */,
+                           const float *params, int64_t W, int64_t M,
+                           const double *FN, const double *FP /* S each */,
+                           const int32_t *order_hint /* N labels or NULL */,
+                           int64_t chunk,
+                           double *sum_ll, double *sum_ll2, double *efn,
+                           double *efp, double *eg1,
+                           int64_t *call1_obs1, int64_t *call1_obs0 /* M each */,
+                           double *ll /* S x M, or NULL */);
+/* diagnostic: one bnpc_post_mutation_fit call without its results' way back,
+ * milliseconds by device events summed over the call - ms[0] the uploads and
+ * the mask kernel, ms[1] the rank kernel, ms[2] the counting kernel (the
+ * subtotals are its tail: ms[3] is 0), ms[4] the per-mutation reduction */
+int bnpc_post_mutation_fit_times(bnpc_post *post, const uint8_t *codes,
+                                 const float *params, int64_t W, int64_t M,
+                                 const double *FN, const double *FP,
+                                 const int32_t *order_hint, int64_t chunk,
+                                 float *ms);
 int bnpc_post_destroy(bnpc_post *post);
 
 #ifdef __cplusplus

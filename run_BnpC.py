@@ -22,7 +22,10 @@ taken from the cell's MPEAR cluster: genotypes_cell_prob_posterior_mean.tsv,
 genotypes_cell_cont_posterior_mean.tsv, genotypes_cell_sd_posterior_mean.tsv;
 -pf (not a reference flag either) writes how well the model explains every
 cell and the run's WAIC, from the log-likelihood of every cell in every
-posterior sample: cell_fit_posterior_mean.tsv, model_fit_posterior_mean.txt.
+posterior sample: cell_fit_posterior_mean.tsv, model_fit_posterior_mean.txt;
+-pm (not a reference flag either) writes how well the model explains every
+mutation and the error rates its column implies:
+mutation_fit_posterior_mean.tsv, mutation_summary_posterior_mean.txt.
 """
 import argparse
 from datetime import datetime
@@ -139,6 +142,13 @@ FLAGS = [
         'posterior samples, per observed entry too - and the WAIC of the '
         'run, with the cell as its unit (needs -e posterior; one more pass '
         'over samples x cells x mutations on the GPU).')),
+    ('output', '-pm', '--posterior_mutations', dict(action='store_true',
+        default=argparse.SUPPRESS, help='Write how well the model explains '
+        'every mutation - mean and spread of its column\'s log-likelihood '
+        'over the posterior samples - and the false-negative and '
+        'false-positive rates the column implies, beside the run\'s global '
+        'pair (needs -e posterior; one more pass over the samples on the '
+        'GPU, over column counts per cluster).')),
 ]
 
 
@@ -148,6 +158,7 @@ class Args(argparse.Namespace):
     posterior_support = False
     posterior_genotypes = False
     posterior_fit = False
+    posterior_mutations = False
 
 
 def build_parser():
@@ -189,6 +200,10 @@ def check_args(args):
         raise SystemExit('-pf / --posterior_fit writes tables of the '
             'posterior samples: it needs `posterior` among the estimators '
             f'(-e), which are: {" ".join(ests)}')
+    if getattr(args, 'posterior_mutations', False) and 'posterior' not in ests:
+        raise SystemExit('-pm / --posterior_mutations writes tables of the '
+            'posterior samples: it needs `posterior` among the estimators '
+            f'(-e), which are: {" ".join(ests)}')
 
 
 def save_outputs(args, results, data, out_dir, names=None):
@@ -207,7 +222,8 @@ def save_outputs(args, results, data, out_dir, names=None):
             inf = postproc.posterior_estimate(results, data,
                 support=getattr(args, 'posterior_support', False),
                 cells=getattr(args, 'posterior_genotypes', False),
-                fit=getattr(args, 'posterior_fit', False))
+                fit=getattr(args, 'posterior_fit', False),
+                mutations=getattr(args, 'posterior_mutations', False))
             rows_a.append(('mean', est,
                 ' '.join(str(i) for i in inf['assignment'])))
             inferred.append(('mean', est, inf))
@@ -223,6 +239,12 @@ def save_outputs(args, results, data, out_dir, names=None):
                     total = inf['fit']['total']
                     print(f'posterior fit: WAIC {total["waic"]:.4f}, lppd '
                         f'{total["lppd"]:.4f}, p_waic {total["p_waic"]:.4f}')
+                if 'mutation_fit' in inf:
+                    total = inf['mutation_fit']['total']
+                    print('posterior mutations: FN_model '
+                        f'{total["FN_model"]:.4f}, FP_model '
+                        f'{total["FP_model"]:.6f} (run: FN {total["FN"]:.4f}, '
+                        f'FP {total["FP"]:.6f})')
             continue
         for chain, res in chains:
             res = res if res is not None else postproc.best_chain(results, est)
@@ -250,7 +272,7 @@ def save_outputs(args, results, data, out_dir, names=None):
             if key == 'time':
                 val = [f'{t:%Y%m%d_%H:%M:%S}' for t in val]
             if key in ('posterior_support', 'posterior_genotypes',
-                    'posterior_fit') and not val:
+                    'posterior_fit', 'posterior_mutations') and not val:
                 continue        # listed only when it is set
             f.write(f'{key}: {val}\n')
     mut_names = names[1] if names is not None else None
@@ -266,6 +288,9 @@ def save_outputs(args, results, data, out_dir, names=None):
         if 'fit' in inf:
             bio.save_cell_fit(out_dir, chain, est, inf['fit'],
                 inf['assignment'], names[0] if names is not None else None)
+        if 'mutation_fit' in inf:
+            bio.save_mutation_fit(out_dir, chain, est, inf['mutation_fit'],
+                mut_names)
     # the metric tables list their rows chain by chain, as the reference
     # does (its per-chain dictionary, dpmmIO.py:524-530); the pooled
     # posterior first

@@ -30,7 +30,14 @@ per-cell fit pass (bnpc_post_cell_fit) over the same trace with random data
 (Posterior.cell_fit_times): the fastest one's uploads and its four kernels,
 the table bytes per second k_cf_sums reads (8 per observed entry, cell and
 sample) beside the trace bytes per second of k_cg_accum (4 per cell, mutation
-and sample), then the call with its results brought to the host; then exit."""
+and sample), then the call with its results brought to the host; then -
+MUT_FIT=1 - the per-mutation fit pass (bnpc_post_mutation_fit) over the same
+trace, data and error rates, CELLS_REPS calls by device events
+(Posterior.mutation_fit_times) for each of three hints - the true clusters
+(sorted), the last sample's labels (the default) and random labels: the
+fastest one's uploads and mask kernel, k_cg_rank, k_mf_count, k_mf_reduce
+beside k_cf_sums of the same run, then the call with its vectors brought to
+the host; then exit."""
 import os
 import sys
 import time
@@ -126,11 +133,14 @@ if CELLS_M:
         t0 = lap('host loop (postproc.host_cell_genotypes)', t0)
         print('  device == host:', all(np.array_equal(g, w)
             for g, w in zip(got, want)))
-    if os.environ.get('CELLS_FIT') == '1':
+    fits = [k for k in ('CELLS_FIT', 'MUT_FIT') if os.environ.get(k) == '1']
+    if fits:
         data = (rng.random_sample((N, CELLS_M)) < 0.3).astype(np.uint8)
         data[rng.random_sample((N, CELLS_M)) < 0.3] = 3
         FN, FP = rng.uniform(0.1, 0.3, S), rng.uniform(1e-4, 1e-2, S)
         seen = int((data != 3).sum()) * S
+        f_sum = None
+    if 'CELLS_FIT' in fits:
         print(f'cell fit: {seen:.3e} observed element-steps of {steps:.3e}, '
             f'LL {S * N * 8 / 1e9:.2f} GB')
         runs = []
@@ -148,6 +158,29 @@ if CELLS_M:
         t0 = time.perf_counter()
         post.cell_fit(data, params, FN, FP, chunk, slab)
         t0 = lap('Posterior.cell_fit (call, three vectors to the host)', t0)
+    if 'MUT_FIT' in fits:
+        if f_sum is None:
+            f_sum = post.cell_fit_times(data, params, FN, FP, chunk, slab)[3]
+        print(f'mutation fit: lane masks {(N + 63) // 64 * CELLS_M * 16 / 1e9:.2f}'
+            f' GB; k_cf_sums of this run {f_sum:.4f} s')
+        hints = (('sorted hint (true clusters)', base),
+            ('no hint (last sample)', None),
+            ('random hint', rng.randint(0, C, N)))
+        for name, hint in hints:
+            runs = []
+            for r in range(reps):
+                t = post.mutation_fit_times(data, params, FN, FP, hint, chunk)
+                runs.append((sum(t),) + t)
+            total, m_up, m_rank, m_cnt, _, m_red = min(runs)
+            print(f'  {name}, fastest of {reps} (device events): pass '
+                f'{total:.4f} s = uploads + k_mf_masks {m_up:.4f} s  '
+                f'k_cg_rank {m_rank:.4f} s  k_mf_count {m_cnt:.4f} s  '
+                f'k_mf_reduce {m_red:.4f} s; k_mf_count / k_cf_sums time '
+                f'{m_cnt / f_sum:.3f}x', flush=True)
+        t0 = time.perf_counter()
+        post.mutation_fit(data, params, FN, FP, base, chunk)
+        t0 = lap('Posterior.mutation_fit (call, seven vectors to the host)',
+            t0)
     post.close()
     sys.exit(0)
 tree = post.ward()
