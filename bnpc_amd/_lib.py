@@ -42,6 +42,8 @@ SUPPORT_KC = 128    # include/bnpc_hip.h: BNPC_SUPPORT_KC (clusters per pass)
 CELL_RANK_LDS_CELLS = 257984
 CELL_TILE = 8       # bnpc_codist.hip: CG_CELLS (cells per workgroup)
 MUT_FIT_ROWS = 32   # bnpc_codist.hip: MF_ROWS (cluster rows of a wave's LDS tile)
+DOUBLET_TILE = 8    # bnpc_codist.hip: DB_TILE (candidates of a wave of k_db_sums)
+DOUBLET_UNROLL = 2  # bnpc_codist.hip: DB_UNROLL (mutations per trip of its loop)
 
 _i64 = C.c_int64
 # array arguments travel as plain addresses (building a typed ctypes pointer
@@ -323,6 +325,12 @@ SIGNATURES = {
         _pd]),
     'bnpc_post_mutation_fit_times': (C.c_int, [C.c_void_p, C.c_void_p, _pf,
         _i64, _i64, _pd, _pd, _pi32, _i64, C.POINTER(C.c_float)]),
+    'bnpc_post_doublets': (C.c_int, [C.c_void_p, C.c_void_p, _i64, _pi32,
+        _i64, _pd, C.c_double, C.c_double, _pd, C.c_double, C.c_double, _i64,
+        _i64, _pd, _pd, _pd, _pd, _pd, _pi32, _pi32, _pd, _pd, _pd]),
+    'bnpc_post_doublets_times': (C.c_int, [C.c_void_p, C.c_void_p, _i64,
+        _pi32, _i64, _pd, C.c_double, C.c_double, _pd, C.c_double, C.c_double,
+        _i64, _i64, C.POINTER(C.c_float)]),
     'bnpc_post_ward': (C.c_int, [C.c_void_p, _pd]),
     'bnpc_post_ward_stats': (C.c_int, [C.c_void_p, C.POINTER(_i64),
         C.POINTER(_i64)]),
@@ -913,6 +921,75 @@ class Posterior:
             ptr(par), par.shape[1], par.shape[2], ptr(FN), ptr(FP),
             None if order is None else ptr(order), int(chunk), ms),
             'post_mutation_fit_times')
+        return tuple(x / 1e3 for x in ms)
+
+    def _doublet_args(self, data, labels, theta, FN, FP, logw):
+        codes = data_codes(data)
+        theta = np.ascontiguousarray(theta, dtype=np.float64)
+        if theta.ndim != 2 or codes.shape != (self.N, theta.shape[1]):
+            raise ValueError(f'the data must be {self.N} cells x the '
+                f'{theta.shape[-1]} mutations of theta, not {codes.shape}')
+        labels = np.ascontiguousarray(labels, dtype=np.int32)
+        if labels.shape != (self.N,):
+            raise ValueError(f'the clustering must hold {self.N} labels')
+        K = theta.shape[0]
+        sizes = np.bincount(labels[(labels >= 0) & (labels < K)], minlength=K)
+        # (an empty cluster: log 0, which the call refuses)
+        with np.errstate(divide='ignore'):
+            if logw is None:
+                logw = np.log(sizes.astype(np.float64))
+            pairs = (int(sizes.sum()) ** 2 - int((sizes ** 2).sum())) // 2
+            lT = float(np.log(np.float64(pairs)))
+        logw = np.ascontiguousarray(logw, dtype=np.float64)
+        if logw.shape != (K,):
+            raise ValueError(f'logw must hold {K} log-weights')
+        return (codes, labels, theta, float(FN), float(FP), logw,
+            float(np.log(np.float64(self.N))), lT)
+
+    def doublets(self, data, labels, theta, FN, FP, logw=None, chunk=0,
+            slab=0, matrix=False, tables=False):
+        """The log-likelihood of every cell under every cluster of a
+        clustering and under every unordered pair of them, reduced per cell
+        (bnpc_post_doublets) -> (own, ll_single, lse_single, ll_pair,
+        lse_pair, best_single, best_pair, scores, L1, L0): five (N,) float64,
+        (N,) int32 and (N, 2) int32, as postproc.host_doublets defines them;
+        with matrix=True, else None, the (N, P) scores; with tables=True,
+        else None, the (P, M) tables L1 and L0 the scores are the sequential
+        sums of.  data: cells x mutations, 0 / 1 / missing (NaN or 3), or its
+        uint8 codes; labels: N labels compact in [0, K), no cluster empty;
+        theta: K x M in [0, 1]; FN, FP: two scalars strictly inside (0, 1);
+        logw: K log-weights (None: the logs of the cluster sizes).  chunk:
+        candidates whose tables are on the device at a time (0: about 512
+        MB); slab: cells whose scores are resident at a time (0: what the
+        free device memory takes).  The same bits for any chunk and slab."""
+        codes, labels, theta, FN, FP, logw, lN, lT = self._doublet_args(data,
+            labels, theta, FN, FP, logw)
+        N, (K, M) = self.N, theta.shape
+        P = K + K * (K - 1) // 2
+        vec = [np.empty(N) for _ in range(5)]
+        best_single = np.empty(N, dtype=np.int32)
+        best_pair = np.empty((N, 2), dtype=np.int32)
+        scores = np.empty((N, P)) if matrix else None
+        L1, L0 = (np.empty((P, M)) if tables else None for _ in range(2))
+        check(load().bnpc_post_doublets(self._h, ptr(codes), M, ptr(labels),
+            K, ptr(theta), FN, FP, ptr(logw), lN, lT, int(chunk), int(slab),
+            *[ptr(x) for x in vec], ptr(best_single), ptr(best_pair),
+            *[None if x is None else ptr(x) for x in (scores, L1, L0)]),
+            'post_doublets')
+        return tuple(vec) + (best_single, best_pair, scores, L1, L0)
+
+    def doublets_times(self, data, labels, theta, FN, FP, logw=None, chunk=0,
+            slab=0):
+        """Seconds by device events, summed over one doublets call that
+        brings nothing back: (uploads and mask kernel, table kernel, sums
+        kernel, per-cell reduction)."""
+        codes, labels, theta, FN, FP, logw, lN, lT = self._doublet_args(data,
+            labels, theta, FN, FP, logw)
+        ms = (C.c_float * 4)()
+        check(load().bnpc_post_doublets_times(self._h, ptr(codes),
+            theta.shape[1], ptr(labels), theta.shape[0], ptr(theta), FN, FP,
+            ptr(logw), lN, lT, int(chunk), int(slab), ms),
+            'post_doublets_times')
         return tuple(x / 1e3 for x in ms)
 
     def close(self):

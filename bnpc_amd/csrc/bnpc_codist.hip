@@ -2947,3 +2947,572 @@ extern "C" int bnpc_post_mutation_fit_times(bnpc_post *p, const uint8_t *codes,
     return mf_run(p, codes, params, W, M, FN, FP, order_hint, chunk, out, iout,
                   nullptr, ms);
 }
+
+// ---------------------------------------------------------------------------
+// Doublet scores (-pd): the log-likelihood of every cell under every single
+// posterior cluster and under every unordered pair of them.  Candidate c < K
+// is the cluster c; then the pairs (a, b), a < b, in lexicographic order,
+// P = K + K (K - 1) / 2 in all.  With theta the K x M cluster genotypes
+// (float64) and one FN, FP:
+//   single  t = theta[k][m], o = 1.0 - t
+//   pair    o = (1.0 - theta[a][m]) * (1.0 - theta[b][m]), t = 1.0 - o
+//   L1 = log(t * (1 - FN) + o * FP)      L0 = log(t * FN + o * (1 - FP))
+// (every operation rounded on its own), score[i][c] the sum over the mutations,
+// strictly in increasing m from 0.0, of L1[c][m] where cell i shows a 1 and
+// L0[c][m] where it shows a 0, and per cell, over its candidates in index
+// order, the reductions of postproc.host_doublets, the host loop this is
+// pinned to.
+//
+// Once per call the data go up, the cells in their own order, and k_mf_masks
+// turns them into the lane masks {ones, zeros}[block of 64 cells][mutation].
+// Per slab of cells and chunk of candidates:
+// k_db_tables  thread = (candidate of the chunk, mutation): L1 and L0 as
+//              T[tile][m][2][DB_TILE], so that what a tile needs at one
+//              mutation is 2 * DB_TILE contiguous doubles
+// k_db_sums    wave = (block of 64 cells, tile of DB_TILE candidates), lane =
+//              cell, DB_TILE accumulators in registers, the loop over the
+//              mutations in increasing m.  The masks and the tile's table
+//              values depend on the wave alone (the wave's number goes
+//              through readfirstlane), so they arrive by scalar loads and
+//              stay in scalar registers.  A lane's weight of L1 is the mask
+//              select w1 = its bit of `ones` ? 1.0 : 0.0 (one v_cndmask on the
+//              scalar mask, once per mutation for the whole tile), w0 likewise
+//              from `zeros`, and per candidate acc = fma(w1, L1, acc),
+//              acc = fma(w0, L0, acc) with the table value as the scalar
+//              operand: fma(1.0, L, acc) is the rounded sum acc + L and
+//              fma(0.0, L, acc) is acc itself (L is finite and acc is never
+//              -0.0), so each score is bit for bit the sequential sum of the
+//              device's own tables.  No atomics, no cross-lane step, no split
+//              of the mutations.  The four waves of a workgroup take
+//              different cell blocks of one tile and share its table lines in
+//              cache.  Results go to SCO[candidate][cell of the slab], which
+//              stays on the device over all chunks.
+// and after the last chunk
+// k_db_reduce  thread = cell: its P scores in candidate order.
+// SCO resident (P x slab x 8 bytes) is what makes the reductions independent
+// of the chunking: the largest weighted score of a group is needed before
+// its exp-sum.
+// ---------------------------------------------------------------------------
+#define DB_TILE 8                   // candidates of a wave: 16 accumulator VGPRs
+#define DB_UNROLL 2                 // mutations per trip of the sums loop
+
+__global__ __launch_bounds__(256) void k_db_tables(
+    const double *__restrict__ theta, long long M,
+    const int2 *__restrict__ pair, int slots, double fn, double fp,
+    double *__restrict__ T)
+{
+    const long long m = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (m >= M) return;
+    for (int q = blockIdx.y; q < slots; q += gridDim.y) {
+        // (a, -1): the single a; (-1, -1): a padding slot of the last tile
+        const int2 ab = pair[q];
+        double l1 = 0.0, l0 = 0.0;
+        if (ab.x >= 0) {
+            double t, o;
+            if (ab.y < 0) {
+                t = theta[(size_t)ab.x * M + m];
+                o = 1.0 - t;
+            } else {
+                o = (1.0 - theta[(size_t)ab.x * M + m])
+                    * (1.0 - theta[(size_t)ab.y * M + m]);
+                t = 1.0 - o;
+            }
+            l1 = log(t * (1.0 - fn) + o * fp);
+            l0 = log(t * fn + o * (1.0 - fp));
+        }
+        double *dst = T + ((size_t)(q / DB_TILE) * M + m) * (2 * DB_TILE)
+            + q % DB_TILE;
+        dst[0] = l1;
+        dst[DB_TILE] = l0;
+    }
+}
+
+// 1.0 in the lanes whose bit of the wave-uniform mask is set, else 0.0
+__device__ __forceinline__ double db_weight(unsigned long long mask)
+{
+    return __builtin_amdgcn_inverse_ballot_w64(mask) ? 1.0 : 0.0;
+}
+
+#define DB_STEP(mm)                                                          \
+    do {                                                                     \
+        const ulonglong2 w_ = mk[mm];                                        \
+        const double w1_ = db_weight(w_.x), w0_ = db_weight(w_.y);           \
+        const double *row_ = tab + (size_t)(mm) * (2 * DB_TILE);             \
+        _Pragma("unroll") for (int j = 0; j < DB_TILE; j++) {                \
+            acc[j] = fma(w1_, row_[j], acc[j]);                              \
+            acc[j] = fma(w0_, row_[DB_TILE + j], acc[j]);                    \
+        }                                                                    \
+    } while (0)
+
+// one chunk of n candidates, the first of them candidate c0: T its tables,
+// masks the [blocks][Mp] lane masks of all cells, b0 the slab's first block,
+// nblk its blocks; SCO the slab's [P][pitch = 64 nblk] scores
+__global__ __launch_bounds__(256) void k_db_sums(
+    const double *__restrict__ T, int n, long long M, long long Mp,
+    const ulonglong2 *__restrict__ masks, long long b0, long long nblk,
+    long long pitch, long long c0, double *__restrict__ SCO)
+{
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int lane = (int)(threadIdx.x & 63);
+    const int tile = (int)blockIdx.x;
+    const double *tab = T + (size_t)tile * M * (2 * DB_TILE);
+    for (long long b = (long long)blockIdx.y * 4 + wave; b < nblk;
+         b += (long long)gridDim.y * 4) {
+        const ulonglong2 *mk = masks + (size_t)(b0 + b) * Mp;
+        double acc[DB_TILE];
+#pragma unroll
+        for (int j = 0; j < DB_TILE; j++) acc[j] = 0.0;
+        long long m = 0;
+        for (; m + DB_UNROLL <= M; m += DB_UNROLL) {
+#pragma unroll
+            for (int u = 0; u < DB_UNROLL; u++) DB_STEP(m + u);
+        }
+        for (; m < M; m++) DB_STEP(m);
+#pragma unroll
+        for (int j = 0; j < DB_TILE; j++)
+            if (tile * DB_TILE + j < n)
+                SCO[(size_t)(c0 + tile * DB_TILE + j) * pitch + b * 64 + lane]
+                    = acc[j];
+    }
+}
+#undef DB_STEP
+
+// cell i of the slab: its column SCO[0 .. P)[off + i] in candidate order.
+// prior[c] is the log-weight of candidate c; the pair of a candidate is
+// carried along the walk
+__global__ __launch_bounds__(256) void k_db_reduce(
+    const double *__restrict__ SCO, long long pitch, long long off,
+    long long nc, const int *__restrict__ labels, int K,
+    const double *__restrict__ prior, double *__restrict__ own,
+    double *__restrict__ ll_single, double *__restrict__ lse_single,
+    double *__restrict__ ll_pair, double *__restrict__ lse_pair,
+    int *__restrict__ best_single, int2 *__restrict__ best_pair)
+{
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= nc) return;
+    const double *col = SCO + off + i;
+    double best = col[0], mx = best + prior[0];
+    int arg = 0;
+    for (int k = 1; k < K; k++) {
+        const double v = col[(size_t)k * pitch];
+        const double y = v + prior[k];
+        if (v > best) {
+            best = v;
+            arg = k;
+        }
+        mx = y > mx ? y : mx;
+    }
+    double es = 0.0;
+    for (int k = 0; k < K; k++)
+        es += exp((col[(size_t)k * pitch] + prior[k]) - mx);
+    own[i] = col[(size_t)labels[i] * pitch];
+    ll_single[i] = best;
+    best_single[i] = arg;
+    lse_single[i] = mx + log(es);
+    if (K < 2) {
+        ll_pair[i] = -INFINITY;
+        lse_pair[i] = -INFINITY;
+        best_pair[i] = make_int2(-1, -1);
+        return;
+    }
+    const double *pcol = col + (size_t)K * pitch;
+    const double *pprior = prior + K;
+    best = pcol[0];
+    mx = best + pprior[0];
+    int2 at = make_int2(0, 1), ab = make_int2(0, 1);
+    long long c = 0;
+    for (;;) {
+        const double v = pcol[(size_t)c * pitch];
+        const double y = v + pprior[c];
+        if (v > best) {
+            best = v;
+            at = ab;
+        }
+        mx = y > mx ? y : mx;
+        c++;
+        if (++ab.y == K) {
+            if (++ab.x == K - 1) break;
+            ab.y = ab.x + 1;
+        }
+    }
+    es = 0.0;
+    for (long long q = 0; q < c; q++)
+        es += exp((pcol[(size_t)q * pitch] + pprior[q]) - mx);
+    ll_pair[i] = best;
+    lse_pair[i] = mx + log(es);
+    best_pair[i] = at;
+}
+
+namespace {
+struct DbOut {
+    double *own, *ll_single, *lse_single, *ll_pair, *lse_pair;
+    int32_t *best_single, *best_pair;
+    double *scores, *L1, *L0;
+};
+}  // namespace
+
+// ms (NULL, or 4 floats): device-event milliseconds summed over the call -
+// ms[0] the uploads and k_mf_masks, ms[1] k_db_tables, ms[2] k_db_sums, ms[3]
+// k_db_reduce
+static int db_run(bnpc_post *p, const uint8_t *codes, int64_t M,
+                  const int32_t *labels, int64_t K, const double *theta,
+                  double FN, double FP, const double *logw, double lN,
+                  double lT, int64_t chunk, int64_t slab, const DbOut &out,
+                  float *ms)
+{
+    if (!p || !codes || !labels || !theta || !logw || M < 1 || K < 1
+        || (M + 255) / 256 > (int64_t)INT_MAX || chunk < 0 || slab < 0) {
+        bnpc_set_error("bad argument: the doublet scores need the data's "
+                       "codes, M >= 1, N labels, K >= 1 x M cluster genotypes, "
+                       "K log-weights, chunk >= 0 and slab >= 0");
+        return 2;
+    }
+    const int64_t N = p->N;
+    // (K (K + 1) / 2 < 2^31 is K < 65536)
+    if (K >= 65536) {
+        bnpc_set_error("doublets: %lld clusters give 2^31 candidates or more",
+                       (long long)K);
+        return 2;
+    }
+    const int64_t P = K + K * (K - 1) / 2;
+    if (!(FN > 0.0 && FN < 1.0 && FP > 0.0 && FP < 1.0)) {
+        bnpc_set_error("doublets: FN = %g, FP = %g are not both inside (0, 1)",
+                       FN, FP);
+        return 2;
+    }
+    if (!std::isfinite(lN) || (K > 1 && !std::isfinite(lT))) {
+        bnpc_set_error("doublets: the log-weights' norms lN = %g, lT = %g are "
+                       "not finite", lN, lT);
+        return 2;
+    }
+    std::vector<int64_t> sizes(K, 0);
+    for (int64_t i = 0; i < N; i++) {
+        if (labels[i] < 0 || labels[i] >= K) {
+            bnpc_set_error("doublets: label %d of cell %lld is not in [0, K = "
+                           "%lld)", (int)labels[i], (long long)i, (long long)K);
+            return 2;
+        }
+        sizes[labels[i]]++;
+    }
+    for (int64_t k = 0; k < K; k++) {
+        if (!sizes[k]) {
+            bnpc_set_error("doublets: cluster %lld is empty", (long long)k);
+            return 2;
+        }
+        if (!std::isfinite(logw[k])) {
+            bnpc_set_error("doublets: the log-weight %g of cluster %lld is not "
+                           "finite", logw[k], (long long)k);
+            return 2;
+        }
+    }
+    for (int64_t at = 0; at < K * M; at++) {
+        if (!(theta[at] >= 0.0 && theta[at] <= 1.0)) {
+            bnpc_set_error("doublets: the genotype %g of cluster %lld at "
+                           "mutation %lld is not in [0, 1]", theta[at],
+                           (long long)(at / M), (long long)(at % M));
+            return 2;
+        }
+    }
+    // the candidates' log-weights, in the definition's arithmetic
+    std::vector<double> prior((size_t)P);
+    for (int64_t k = 0; k < K; k++) prior[k] = logw[k] - lN;
+    {
+        size_t c = (size_t)K;
+        for (int64_t a = 0; a < K; a++)
+            for (int64_t b = a + 1; b < K; b++)
+                prior[c++] = (logw[a] + logw[b]) - lT;
+    }
+
+    PCK(hipSetDevice(p->device));
+    GtBuffers buf;
+    CgEvents evs;
+    auto oom = [](hipError_t e) {
+        (void)hipGetLastError();
+        bnpc_set_error("doublets: out of device memory (%s)",
+                       hipGetErrorString(e));
+        return 5;
+    };
+#define DBA(expr)                                                            \
+    do {                                                                     \
+        hipError_t a_ = (expr);                                              \
+        if (a_ == hipErrorOutOfMemory) return oom(a_);                       \
+        PCK(a_);                                                             \
+    } while (0)
+
+    // the working set: the lane masks of all cells, a slab of the data while
+    // they are built, the genotypes, a chunk's tables, and per resident cell
+    // its P scores and seven results
+    const int64_t nb = (N + 63) / 64;
+    const int64_t Mp = (M + 63) / 64 * 64;
+    const int64_t code_blocks = std::min<int64_t>(std::min<int64_t>(nb, 65535),
+        std::max<int64_t>(1, (int64_t)(((size_t)64 << 20) / ((size_t)M * 64))));
+    const int64_t code_cells = code_blocks * 64;
+    // (a launch's first dimension times its 256 threads stays below 2^32)
+    const int64_t chunk_max = std::min<int64_t>(P, (int64_t)1 << 24);
+    int64_t sc = chunk ? std::min(chunk, chunk_max)
+                       : std::min<int64_t>(chunk_max, std::max<int64_t>(DB_TILE,
+                             (int64_t)(((size_t)512 << 20) / ((size_t)M * 16))));
+    const size_t per_cell = (size_t)P * 8 + 56;
+    size_t free_b = 0, total_b = 0;
+    PCK(hipMemGetInfo(&free_b, &total_b));
+    auto fixed = [&](int64_t cands) {
+        const size_t tiles = (size_t)((cands + DB_TILE - 1) / DB_TILE);
+        return (size_t)nb * Mp * 16 + (size_t)code_cells * M
+            + (size_t)K * M * 8 + tiles * M * (16 * DB_TILE)
+            + tiles * DB_TILE * 8 + (size_t)P * 8 + (size_t)N * 4
+            + ((size_t)64 << 20);
+    };
+    // (an unaligned slab of nc cells touches (nc + 62) / 64 + 1 blocks)
+    auto blocks_of = [](int64_t nc) { return (nc + 62) / 64 + 1; };
+    auto room = [&](int64_t cands) {
+        const size_t f = fixed(cands);
+        return free_b > f ? (int64_t)((free_b - f) / per_cell) : (int64_t)0;
+    };
+    // (the pitch of nc cells is below nc + 128)
+    if (!chunk && room(sc) < 192) sc = std::min<int64_t>(sc, DB_TILE);
+    const int64_t fit = room(sc) - 128;
+    int64_t nc;
+    if (slab) {
+        nc = std::min(slab, N);
+        if (nc > fit) nc = 0;
+    } else {
+        nc = std::min(N, fit);
+        if (nc < N) nc = nc / 64 * 64;          // whole blocks
+    }
+    if (nc < 1) {
+        bnpc_set_error("doublets: %lld candidates x 64 cells beside a chunk of "
+                       "%lld candidates x %lld mutations need %.1f GB, %.1f GB "
+                       "of device memory are free", (long long)P,
+                       (long long)sc, (long long)M,
+                       (fixed(sc) + 128.0 * per_cell) / 1e9, free_b / 1e9);
+        return 5;
+    }
+    const int64_t tiles_c = (sc + DB_TILE - 1) / DB_TILE;
+    const int64_t slots = tiles_c * DB_TILE;
+    const int64_t nblk_max = nc >= N ? nb : blocks_of(nc);
+    const int64_t pitch = nblk_max * 64;
+    ulonglong2 *d_masks;
+    uint8_t *d_codes;
+    unsigned long long *d_bad;
+    int2 *d_pair, *d_bp;
+    int *d_labels, *d_bs;
+    double *d_theta, *d_T, *d_prior, *d_SC, *d_res;
+    DBA(buf.alloc(&d_masks, (size_t)nb * Mp));
+    DBA(buf.alloc(&d_codes, (size_t)code_cells * M));
+    DBA(buf.alloc(&d_bad, 1));
+    DBA(buf.alloc(&d_theta, (size_t)K * M));
+    DBA(buf.alloc(&d_T, (size_t)tiles_c * M * (2 * DB_TILE)));
+    DBA(buf.alloc(&d_pair, (size_t)slots));
+    DBA(buf.alloc(&d_prior, (size_t)P));
+    DBA(buf.alloc(&d_labels, (size_t)N));
+    DBA(buf.alloc(&d_SC, (size_t)P * pitch));
+    DBA(buf.alloc(&d_res, (size_t)5 * nc));
+    DBA(buf.alloc(&d_bs, (size_t)nc));
+    DBA(buf.alloc(&d_bp, (size_t)nc));
+#undef DBA
+    if (ms) {
+        for (int k = 0; k < 4; k++) ms[k] = 0.0f;
+        PCK(hipEventCreate(&evs.ev[0]));
+        PCK(hipEventCreate(&evs.ev[1]));
+    }
+    // a lap of the device's clock: begin(), the work, end(its slot of ms)
+    int lap_rc = 0;
+    auto begin = [&]() {
+        if (ms && hipEventRecord(evs.ev[0], 0) != hipSuccess) lap_rc = 1;
+    };
+    auto end = [&](int which) {
+        if (!ms) return;
+        float t = 0.0f;
+        if (hipEventRecord(evs.ev[1], 0) != hipSuccess
+            || hipEventSynchronize(evs.ev[1]) != hipSuccess
+            || hipEventElapsedTime(&t, evs.ev[0], evs.ev[1]) != hipSuccess)
+            lap_rc = 1;
+        ms[which] += t;
+    };
+
+    // the lane masks of all cells, a slab of the data at a time: every code
+    // is looked at before anything is written
+    PCK(hipMemset(d_bad, 0xff, sizeof(unsigned long long)));
+    for (int64_t j0 = 0; j0 < N; j0 += code_cells) {
+        const int64_t cells = std::min(code_cells, N - j0);
+        begin();
+        PCK(hipMemcpy(d_codes, codes + (size_t)j0 * M, (size_t)cells * M,
+                      hipMemcpyHostToDevice));
+        hipLaunchKernelGGL(k_mf_masks,
+                           dim3((unsigned)((Mp + 255) / 256),
+                                (unsigned)((cells + 63) / 64)),
+                           dim3(256), 0, 0, d_codes, (long long)cells,
+                           (long long)M, (long long)Mp,
+                           d_masks + (size_t)(j0 / 64) * Mp, d_bad);
+        PCK(hipGetLastError());
+        end(0);
+        unsigned long long bad = 0;
+        PCK(hipMemcpy(&bad, d_bad, sizeof(bad), hipMemcpyDeviceToHost));
+        if (bad != ~0ull) {
+            const int64_t i = j0 + (int64_t)(bad / (unsigned long long)M);
+            const int64_t m = (int64_t)(bad % (unsigned long long)M);
+            bnpc_set_error("doublets: code %d of cell %lld at mutation %lld is "
+                           "not 0, 1 or 3", (int)codes[(size_t)i * M + m],
+                           (long long)i, (long long)m);
+            return 2;
+        }
+    }
+    begin();
+    PCK(hipMemcpy(d_theta, theta, (size_t)K * M * sizeof(double),
+                  hipMemcpyHostToDevice));
+    PCK(hipMemcpy(d_prior, prior.data(), (size_t)P * sizeof(double),
+                  hipMemcpyHostToDevice));
+    PCK(hipMemcpy(d_labels, labels, (size_t)N * sizeof(int),
+                  hipMemcpyHostToDevice));
+    end(0);
+
+    std::vector<int2> pairs((size_t)slots);
+    std::vector<double> stage;
+    const bool one_chunk = sc >= P;
+    for (int64_t i0 = 0; i0 < N; i0 += nc) {
+        const int64_t cells = std::min(nc, N - i0);
+        const int64_t b0 = i0 / 64, off = i0 - b0 * 64;
+        const int64_t nblk = (i0 + cells - 1) / 64 - b0 + 1;
+        // the walk over the candidates: (a, -1) the singles, then the pairs
+        int64_t a = 0, b = -1;
+        for (int64_t c0 = 0; c0 < P; c0 += sc) {
+            const int64_t n = std::min(sc, P - c0);
+            const int64_t tiles = (n + DB_TILE - 1) / DB_TILE;
+            if (!one_chunk || i0 == 0) {
+                for (int64_t q = 0; q < tiles * DB_TILE; q++) {
+                    if (q >= n) {
+                        pairs[q] = make_int2(-1, -1);
+                        continue;
+                    }
+                    pairs[q] = make_int2((int)a, (int)b);
+                    if (b < 0) {            // the next single, or pair (0, 1)
+                        if (++a == K) {
+                            a = 0;
+                            b = 1;
+                        }
+                    } else if (++b == K) {
+                        a++;
+                        b = a + 1;
+                    }
+                }
+                begin();
+                PCK(hipMemcpy(d_pair, pairs.data(),
+                              (size_t)tiles * DB_TILE * sizeof(int2),
+                              hipMemcpyHostToDevice));
+                end(0);
+                begin();
+                hipLaunchKernelGGL(k_db_tables,
+                                   dim3((unsigned)((M + 255) / 256),
+                                        (unsigned)std::min<int64_t>(
+                                            tiles * DB_TILE, 65535)),
+                                   dim3(256), 0, 0, d_theta, (long long)M,
+                                   d_pair, (int)(tiles * DB_TILE), FN, FP, d_T);
+                PCK(hipGetLastError());
+                end(1);
+                if (i0 == 0 && (out.L1 || out.L0)) {
+                    stage.resize((size_t)tiles * M * (2 * DB_TILE));
+                    PCK(hipMemcpy(stage.data(), d_T,
+                                  stage.size() * sizeof(double),
+                                  hipMemcpyDeviceToHost));
+                    for (int64_t q = 0; q < n; q++) {
+                        const double *src = stage.data()
+                            + (size_t)(q / DB_TILE) * M * (2 * DB_TILE)
+                            + q % DB_TILE;
+                        for (int64_t m = 0; m < M; m++) {
+                            if (out.L1)
+                                out.L1[(size_t)(c0 + q) * M + m]
+                                    = src[(size_t)m * (2 * DB_TILE)];
+                            if (out.L0)
+                                out.L0[(size_t)(c0 + q) * M + m]
+                                    = src[(size_t)m * (2 * DB_TILE) + DB_TILE];
+                        }
+                    }
+                }
+            }
+            begin();
+            hipLaunchKernelGGL(k_db_sums,
+                               dim3((unsigned)tiles,
+                                    (unsigned)std::min<int64_t>((nblk + 3) / 4,
+                                                                65535)),
+                               dim3(256), 0, 0, d_T, (int)n, (long long)M,
+                               (long long)Mp, d_masks, (long long)b0,
+                               (long long)nblk, (long long)pitch,
+                               (long long)c0, d_SC);
+            PCK(hipGetLastError());
+            end(2);
+        }
+        begin();
+        hipLaunchKernelGGL(k_db_reduce, dim3((unsigned)((cells + 255) / 256)),
+                           dim3(256), 0, 0, d_SC, (long long)pitch,
+                           (long long)off, (long long)cells, d_labels + i0,
+                           (int)K, d_prior, d_res, d_res + nc, d_res + 2 * nc,
+                           d_res + 3 * nc, d_res + 4 * nc, d_bs, d_bp);
+        PCK(hipGetLastError());
+        end(3);
+        double *host[5] = {out.own, out.ll_single, out.lse_single, out.ll_pair,
+                           out.lse_pair};
+        for (int k = 0; k < 5; k++)
+            if (host[k])
+                PCK(hipMemcpy(host[k] + i0, d_res + (size_t)k * nc,
+                              cells * sizeof(double), hipMemcpyDeviceToHost));
+        if (out.best_single)
+            PCK(hipMemcpy(out.best_single + i0, d_bs, cells * sizeof(int),
+                          hipMemcpyDeviceToHost));
+        if (out.best_pair)
+            PCK(hipMemcpy(out.best_pair + 2 * i0, d_bp, cells * sizeof(int2),
+                          hipMemcpyDeviceToHost));
+        if (out.scores) {
+            // SCO is [candidate][cell]: through the host, turned
+            stage.resize((size_t)P * cells);
+            PCK(hipMemcpy2D(stage.data(), (size_t)cells * sizeof(double),
+                            d_SC + off, (size_t)pitch * sizeof(double),
+                            (size_t)cells * sizeof(double), (size_t)P,
+                            hipMemcpyDeviceToHost));
+            for (int64_t c = 0; c < P; c++)
+                for (int64_t i = 0; i < cells; i++)
+                    out.scores[(size_t)(i0 + i) * P + c]
+                        = stage[(size_t)c * cells + i];
+        }
+    }
+    PCK(hipDeviceSynchronize());
+    if (lap_rc) {
+        bnpc_set_error("doublets: the device events failed");
+        return 1;
+    }
+    return 0;
+}
+
+extern "C" int bnpc_post_doublets(bnpc_post *p, const uint8_t *codes,
+                                  int64_t M, const int32_t *labels, int64_t K,
+                                  const double *theta, double FN, double FP,
+                                  const double *logw, double lN, double lT,
+                                  int64_t chunk, int64_t slab, double *own,
+                                  double *ll_single, double *lse_single,
+                                  double *ll_pair, double *lse_pair,
+                                  int32_t *best_single, int32_t *best_pair,
+                                  double *scores, double *L1, double *L0)
+{
+    const DbOut out = {own, ll_single, lse_single, ll_pair, lse_pair,
+                       best_single, best_pair, scores, L1, L0};
+    return db_run(p, codes, M, labels, K, theta, FN, FP, logw, lN, lT, chunk,
+                  slab, out, nullptr);
+}
+
+// diagnostic (tools/posterior_bench.py): one bnpc_post_doublets call without
+// its results' way back, by device events (see db_run)
+extern "C" int bnpc_post_doublets_times(bnpc_post *p, const uint8_t *codes,
+                                        int64_t M, const int32_t *labels,
+                                        int64_t K, const double *theta,
+                                        double FN, double FP,
+                                        const double *logw, double lN,
+                                        double lT, int64_t chunk, int64_t slab,
+                                        float *ms)
+{
+    if (!ms) {
+        bnpc_set_error("bad argument: NULL");
+        return 2;
+    }
+    const DbOut out = {};
+    return db_run(p, codes, M, labels, K, theta, FN, FP, logw, lN, lT, chunk,
+                  slab, out, ms);
+}

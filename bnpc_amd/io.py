@@ -418,6 +418,50 @@ def save_mutation_fit(out_dir, chain, est, fit, names=None):
     return paths
 
 
+def save_doublets(out_dir, chain, est, tables, names=None):
+    """The -pd files of postproc.doublets for one (chain, estimator) row.
+    doublets_<est>_<chain>.tsv: per cell its name (`names`, the loader's cell
+    names, when there is one per cell, else 0..N-1), `cluster` (its label of
+    assignment.txt, as every cluster id here), `n_obs`, `ll_cluster`,
+    `best_cluster`, `ll_best`, `pair_a`, `pair_b`, `ll_pair`, `delta`,
+    `p_doublet`; floats %.4f.  doublet_summary_<est>_<chain>.txt: `key:
+    value` lines - cells, clusters, candidates, rate, expected_doublets,
+    called, pair_counts (the pairs with called cells as a-b:count) and
+    top_cells, the ten cells with the largest p_doublet (ties: the larger
+    delta, then the smaller index) as name:value pairs."""
+    N = tables['p_doublet'].size
+    index = np.arange(N)
+    if names is not None and np.asarray(names).size == N:
+        index = np.asarray(names)
+    index = index.tolist()
+    tag = f'{chain:0>2}'
+    paths = [os.path.join(out_dir, f'doublets_{est}_{tag}.tsv'),
+        os.path.join(out_dir, f'doublet_summary_{est}_{tag}.txt')]
+    columns = ('cluster', 'n_obs', 'll_cluster', 'best_cluster', 'll_best',
+        'pair_a', 'pair_b', 'll_pair', 'delta', 'p_doublet')
+    whole = ('cluster', 'n_obs', 'best_cluster', 'pair_a', 'pair_b')
+    with open(paths[0], 'w') as f:
+        f.write('cell\t' + '\t'.join(columns) + '\n')
+        for i, name in enumerate(index):
+            f.write(f'{name}\t' + '\t'.join(str(int(tables[k][i]))
+                if k in whole else f'{tables[k][i]:.4f}' for k in columns)
+                + '\n')
+    total = tables['total']
+    p, delta = tables['p_doublet'], tables['delta']
+    top = sorted(range(N), key=lambda i: (-p[i], -delta[i], i))[:10]
+    with open(paths[1], 'w') as f:
+        for key in ('cells', 'clusters', 'candidates'):
+            f.write(f'{key}: {total[key]}\n')
+        f.write(f'rate: {total["rate"]}\n')
+        f.write(f'expected_doublets: {total["expected_doublets"]:.4f}\n')
+        f.write(f'called: {total["called"]}\n')
+        f.write('pair_counts: ' + ' '.join(f'{a}-{b}:{n}'
+            for (a, b), n in total['pair_counts'].items()) + '\n')
+        f.write('top_cells: ' + ' '.join(f'{index[i]}:{p[i]:.4f}'
+            for i in top) + '\n')
+    return paths
+
+
 def save_metric(path, column, rows):
     """V_measure.txt / ARI.txt / hammingDist.txt (dpmmIO.py:514-542): a
     tab-separated `chain  estimator  <column>` table, floats as to_csv

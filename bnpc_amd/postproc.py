@@ -27,6 +27,10 @@ device pass over the samples, the parameter trace and the data
 The -pm tables (per-mutation posterior fit and the error rates every column
 implies - not a reference output) are a device pass over the same inputs
 (bnpc_post_mutation_fit; host_mutation_fit is the host loop it is pinned to).
+The -pd tables (doublet scores: every cell against every cluster of the MPEAR
+clustering and every pair of them - not a reference output) are a device pass
+over the data and the cluster genotypes (bnpc_post_doublets; host_doublets is
+the host loop it is pinned to).
 The -tc / -td metrics (V-measure, ARI, Hamming; utils.py:49-72) are
 restated from integer counts at the end; tree helpers are out of scope.
 """
@@ -323,9 +327,12 @@ def mean_hierarchy_assignment(assignments, params_full, dist=None):
     return assign, params[assign].T
 
 
-def _mean_hierarchy(assignments, params_full, dist=None, while_open=None):
+def _mean_hierarchy(assignments, params_full, dist=None, while_open=None,
+        with_genotypes=None):
     """(MPEAR clustering, per-cluster mean parameters (clusters, muts));
-    while_open(post, assign) is called before the Posterior is closed."""
+    while_open(post, assign) is called before the genotype pass and
+    with_genotypes(post, assign, params) after it, both before the Posterior
+    is closed."""
     assign, post = _mpear(assignments, dist)
     # the device pass runs on the samples the Posterior holds on the device;
     # a clustering handle without it (a host stand-in for the pair counts)
@@ -339,6 +346,8 @@ def _mean_hierarchy(assignments, params_full, dist=None, while_open=None):
             params = device(assign, params_full)
         else:
             params = host_genotypes(assignments, assign, params_full)
+        if with_genotypes is not None:
+            with_genotypes(post, assign, params)
     finally:
         if post is not None:
             post.close()
@@ -392,7 +401,7 @@ def concat_chain_results(results):
 
 
 def posterior_estimate(results, data, support=False, cells=False, fit=False,
-        mutations=False):
+        mutations=False, doublets=False):
     """`-e posterior` (the default estimator), chains pooled
     (utils.py:195-244).  support=True: the key 'support' holds the tables of
     cluster_support for the MPEAR clustering, made from the pair counts of
@@ -402,9 +411,18 @@ def posterior_estimate(results, data, support=False, cells=False, fit=False,
     holds the tables of cell_fit, from the same samples, the data and the
     samples' error rates.  mutations=True: the key 'mutation_fit' holds the
     tables of mutation_fit, from the same inputs, the cells sorted by the
-    MPEAR clustering."""
+    MPEAR clustering.  doublets: a rate in (0, 1), the prior share of
+    doublets among the cells, adds the key 'doublets' with the tables of
+    doublets(), made from the data, the MPEAR clustering, its genotypes and
+    the posterior means of the error rates on the same handle."""
     res = concat_chain_results(results)
     tables = {}
+    if doublets:
+        def with_genotypes(post, assign, params):
+            tables['doublets'] = _doublet_tables(post, data, assign,
+                params, np.mean(res['FN']), np.mean(res['FP']), doublets)
+    else:
+        with_genotypes = None
     if support or cells or fit or mutations:
         def while_open(post, assign):
             if support:
@@ -422,7 +440,7 @@ def posterior_estimate(results, data, support=False, cells=False, fit=False,
     else:
         while_open = None
     assign, params = _mean_hierarchy(res['assignments'], res['params'],
-        while_open=while_open)
+        while_open=while_open, with_genotypes=with_genotypes)
     geno = params[assign].T
     called = geno.T.round()
     FN_geno = (((called == 1) & (data == 0)).sum() + EPSILON) \
@@ -821,6 +839,186 @@ def mutation_fit(post, data, assignments, params_full, FN, FP, order=None):
         'prevalence': _rate(eg1, S * n_obs),
         **rates(n_obs, n1, efn, efp, eg1, c11, c10), 'eg1': eg1,
         'total': total}
+
+
+# ---------------------------------------------------------------------------
+# doublet scores (-pd): is a cell explained by two clusters at once?  Every
+# cell against every cluster of a clustering and every unordered pair of them;
+# not a reference output, so the arithmetic and the summation order below are
+# the specification
+# ---------------------------------------------------------------------------
+def doublet_pairs(K):
+    """The pairs (a, b), a < b, of K clusters in lexicographic order: (a, b)
+    int64 arrays of K (K - 1) / 2.  Pair (a, b) is candidate
+    K + a (2K - a - 1) / 2 + (b - a - 1); the K singles come first."""
+    a, b = np.triu_indices(K, 1)
+    return a.astype(np.int64), b.astype(np.int64)
+
+
+def doublet_tables(theta, FN, FP):
+    """The (P, M) float64 tables L1, L0 of host_doublets: the K singles, then
+    the pairs."""
+    theta = np.asarray(theta, dtype=np.float64)
+    a, b = doublet_pairs(theta.shape[0])
+    o = np.concatenate([1.0 - theta, (1.0 - theta[a]) * (1.0 - theta[b])])
+    t = np.concatenate([theta, 1.0 - o[theta.shape[0]:]])
+    return np.log(t * (1 - FN) + o * FP), np.log(t * FN + o * (1 - FP))
+
+
+def doublet_reduce(scores, labels, K, logw, lN, lT):
+    """host_doublets' per-cell reductions of an (N, P) matrix of scores, each
+    a walk over the cell's candidates in index order."""
+    scores = np.asarray(scores, dtype=np.float64)
+    N, P = scores.shape
+    a, b = doublet_pairs(K)
+
+    def group(sc, prior):
+        best = np.argmax(sc, axis=1)            # the first of the largest
+        y = sc + prior
+        mx = y.max(axis=1)
+        es = np.zeros(N)
+        for c in range(sc.shape[1]):
+            es += np.exp(y[:, c] - mx)
+        return best, sc[np.arange(N), best], mx + np.log(es)
+    best, ll_single, lse_single = group(scores[:, :K], logw - lN)
+    out = {'own': scores[np.arange(N), labels],
+        'best_single': best.astype(np.int32), 'll_single': ll_single,
+        'lse_single': lse_single}
+    if K > 1:
+        best, ll_pair, lse_pair = group(scores[:, K:], (logw[a] + logw[b]) - lT)
+        best_pair = np.stack([a[best], b[best]], axis=1).astype(np.int32)
+    else:
+        best_pair = np.full((N, 2), -1, dtype=np.int32)
+        ll_pair, lse_pair = np.full(N, -np.inf), np.full(N, -np.inf)
+    out.update(best_pair=best_pair, ll_pair=ll_pair, lse_pair=lse_pair)
+    return out
+
+
+def _doublet_weights(labels, K, logw):
+    """(labels, logw, lN, lT) of host_doublets: the default log-weights are
+    the logs of the cluster sizes, lN = log N, lT = log of the sum of
+    n_a n_b over a < b (-inf for K = 1)."""
+    labels = np.asarray(labels)
+    sizes = np.bincount(labels, minlength=K) if labels.size \
+        and labels.min() >= 0 else np.zeros(K + 1, dtype=np.int64)
+    if sizes.size != K or not sizes.all():
+        raise ValueError(f'the labels must be compact in [0, {K}) with no '
+            'empty cluster')
+    logw = np.log(sizes.astype(np.float64)) if logw is None \
+        else np.asarray(logw, dtype=np.float64)
+    if logw.shape != (K,) or not np.isfinite(logw).all():
+        raise ValueError(f'logw must hold {K} finite log-weights')
+    n = int(labels.size)
+    both = (n * n - int((sizes.astype(object) ** 2).sum())) // 2
+    with np.errstate(divide='ignore'):
+        return labels, logw, np.log(np.float64(n)), np.log(np.float64(both))
+
+
+def host_doublets(data, labels, theta, FN, FP, logw=None):
+    """The log-likelihood of every cell under every single cluster and under
+    every unordered pair of clusters, and its per-cell reductions; the plain
+    loop bnpc_post_doublets is pinned to.  data: cells x mutations, 0 / 1 /
+    missing (NaN or 3); labels: N labels, compact in [0, K), no cluster
+    empty; theta: K x M float64 in [0, 1]; FN, FP: two scalars strictly
+    inside (0, 1).  Candidate c < K is the cluster c; then the pairs (a, b),
+    a < b, in lexicographic order (doublet_pairs); P = K + K (K - 1) / 2.
+      single  t = theta[k][m], o = 1.0 - t
+      pair    o = (1.0 - theta[a][m]) * (1.0 - theta[b][m]), t = 1.0 - o
+              (the union: the mutation is there if either cell carries it)
+      L1 = log(t * (1 - FN) + o * FP)       an observed 1
+      L0 = log(t * FN + o * (1 - FP))       an observed 0
+    (float64, each operation rounded on its own).  scores[i][c] is the sum
+    over the mutations, strictly in increasing m from 0.0, of L1[c][m] where
+    the cell shows a 1 and L0[c][m] where it shows a 0.  With logw the K
+    log-weights (None: log n_k, the cluster sizes), lN = log N and lT = log
+    of the sum of n_a n_b over a < b - the priors of drawing one cell, or two
+    cells of different clusters - a single weighs y = score + (logw[k] - lN)
+    and a pair y = score + ((logw[a] + logw[b]) - lT).  Per cell, over its
+    candidates in index order: 'own' (the score of its own cluster),
+    'best_single' and 'll_single' (the largest single score and its cluster,
+    the first on ties), 'best_pair' (a, b) and 'll_pair' (the same over the
+    pairs), 'lse_single' and 'lse_pair' (mx + log(sum of exp(y - mx)), mx the
+    group's largest y).  K = 1 has no pair: best_pair (-1, -1), ll_pair and
+    lse_pair -inf.
+    -> these and 'scores' (N, P), 'n_obs' (N,) int64"""
+    codes = data_codes(data)
+    theta = np.asarray(theta, dtype=np.float64)
+    K = theta.shape[0]
+    if theta.ndim != 2 or codes.shape[1] != theta.shape[1] \
+            or not ((theta >= 0) & (theta <= 1)).all():
+        raise ValueError('theta must be K x M values in [0, 1]')
+    if not (0 < FN < 1 and 0 < FP < 1):
+        raise ValueError('FN and FP must lie strictly inside (0, 1)')
+    labels, logw, lN, lT = _doublet_weights(labels, K, logw)
+    if labels.shape != (codes.shape[0],):
+        raise ValueError('one label per cell')
+    L1, L0 = doublet_tables(theta, FN, FP)
+    is1, is0 = codes == 1, codes == 0
+    scores = np.zeros((codes.shape[0], L1.shape[0]))
+    for m in range(codes.shape[1]):
+        # (adding 0.0 leaves every bit: no partial sum is -0.0)
+        scores += np.where(is1[:, m, None], L1[:, m],
+            np.where(is0[:, m, None], L0[:, m], 0.0))
+    return {'scores': scores, 'n_obs': (codes != 3).sum(axis=1).astype(np.int64),
+        **doublet_reduce(scores, labels, K, logw, lN, lT)}
+
+
+def doublets(post, data, labels, theta, FN, FP, rate):
+    """The -pd tables: is a cell explained by two clusters at once?  A
+    doublet shows the union of two clones' mutations.  Per cell, (N,) arrays:
+    'cluster' (its label), 'n_obs', 'll_cluster' (its score under its own
+    cluster), 'best_cluster' and 'll_best' (the best single cluster),
+    'pair_a', 'pair_b' and 'll_pair' (the best pair; -1, -1, -inf for one
+    cluster), 'delta' = ll_pair - ll_best, and 'p_doublet' =
+    1 / (1 + exp((log(1 - rate) + lse_single) - (log(rate) + lse_pair))), the
+    posterior probability of a doublet under the prior share `rate` (0 where
+    there is one cluster).  'total': {'cells', 'clusters', 'candidates',
+    'rate', 'expected_doublets' (the sum of p_doublet), 'called' (cells with
+    p_doublet > 0.5), 'pair_counts' ({(a, b): called cells whose best pair it
+    is})}.  From an open clustering handle: the device pass
+    (Posterior.doublets) where the handle has one, else the host loop
+    (host_doublets); the same arithmetic on the reductions either way."""
+    if not 0 < rate < 1:
+        raise ValueError(f'the doublet rate {rate} is not inside (0, 1)')
+    codes = data_codes(data)
+    theta = np.asarray(theta, dtype=np.float64)
+    K = int(theta.shape[0])
+    labels = np.asarray(labels)
+    FN, FP = float(FN), float(FP)
+    device = getattr(post, 'doublets', None)
+    if device is not None:
+        own, ll_single, lse_single, ll_pair, lse_pair, best_single, \
+            best_pair = device(codes, labels, theta, FN, FP)[:7]
+    else:
+        red = host_doublets(codes, labels, theta, FN, FP)
+        own, ll_single, lse_single, ll_pair, lse_pair, best_single, \
+            best_pair = (red[k] for k in ('own', 'll_single', 'lse_single',
+                'll_pair', 'lse_pair', 'best_single', 'best_pair'))
+    N = codes.shape[0]
+    if K > 1:
+        with np.errstate(over='ignore'):
+            p = 1 / (1 + np.exp((np.log(1 - rate) + lse_single)
+                - (np.log(rate) + lse_pair)))
+        delta = ll_pair - ll_single
+    else:
+        p, delta = np.zeros(N), np.full(N, -np.inf)
+    called = p > 0.5
+    pair_counts = {}
+    for a, b in best_pair[called].tolist():
+        pair_counts[(a, b)] = pair_counts.get((a, b), 0) + 1
+    return {'cluster': labels, 'n_obs': (codes != 3).sum(axis=1)
+            .astype(np.int64), 'll_cluster': own,
+        'best_cluster': np.asarray(best_single), 'll_best': ll_single,
+        'pair_a': np.asarray(best_pair)[:, 0],
+        'pair_b': np.asarray(best_pair)[:, 1], 'll_pair': ll_pair,
+        'delta': delta, 'p_doublet': p,
+        'total': {'cells': int(N), 'clusters': K,
+            'candidates': K + K * (K - 1) // 2, 'rate': float(rate),
+            'expected_doublets': float(p.sum()), 'called': int(called.sum()),
+            'pair_counts': dict(sorted(pair_counts.items()))}}
+
+
+_doublet_tables = doublets      # (posterior_estimate's keyword has the name)
 
 
 # ---------------------------------------------------------------------------

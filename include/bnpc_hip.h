@@ -1157,6 +1157,61 @@ int bnpc_post_mutation_fit_times(bnpc_post *post, const uint8_t *codes,
                                  const double *FN, const double *FP,
                                  const int32_t *order_hint, int64_t chunk,
                                  float *ms);
+/* Doublet scores (-pd; not a reference output): the log-likelihood of every
+ * cell under every single cluster of a clustering and under every unordered
+ * pair of them, and its per-cell reductions.  The handle gives the device and
+ * N; its samples are not read.  labels: the N labels of the clustering,
+ * compact in [0, K), no cluster empty; theta: its K x M genotypes in [0, 1];
+ * FN, FP strictly inside (0, 1).  Candidate c < K is the cluster c, then come
+ * the pairs (a, b), a < b, in lexicographic order, the pair's index
+ * K + a (2K - a - 1) / 2 + (b - a - 1); P = K + K (K - 1) / 2 candidates.
+ *   single  t = theta[k][m], o = 1.0 - t
+ *   pair    o = (1.0 - theta[a][m]) * (1.0 - theta[b][m]), t = 1.0 - o
+ *   L1 = log(t * (1 - FN) + o * FP),  L0 = log(t * FN + o * (1 - FP))
+ * (every operation rounded on its own), and
+ *   scores[i][c]  the sum over the mutations, strictly in increasing m from
+ *                 0.0, of L1[c][m] where codes[i][m] == 1 and L0[c][m] where
+ *                 it is 0 (3: missing, nothing): bit for bit the sequential
+ *                 sum of the returned tables
+ *   y             scores[i][k] + (logw[k] - lN) for a single,
+ *                 scores[i][c] + ((logw[a] + logw[b]) - lT) for a pair
+ *   own[i]        scores[i][labels[i]]
+ *   ll_single[i], best_single[i]  the largest single score and its cluster,
+ *                 the first on ties; ll_pair[i], best_pair[i] = (a, b) the
+ *                 same over the pairs
+ *   lse_single[i], lse_pair[i]  mx + log(sum of exp(y - mx)) over the group in
+ *                 index order, mx the group's largest y
+ * as bnpc_amd.postproc.host_doublets defines them.  K = 1 has no pair:
+ * best_pair (-1, -1), ll_pair and lse_pair -inf, lT unused.  chunk: the
+ * candidates whose tables are on the device at a time (0: about 512 MB of
+ * tables); slab: the cells whose P scores are on the device at a time (0: as
+ * many as the free device memory takes beside a chunk).  Every output has the
+ * same bits for any chunk and slab, on every call.  The seven vectors (N
+ * each, best_pair N x 2), scores (N x P) and the tables L1, L0 (P x M each)
+ * may each be NULL.  Return code 2, and no output written, for a label out of
+ * range or an empty cluster, a theta outside [0, 1] or NaN, FN or FP not
+ * strictly inside (0, 1), a non-finite logw, lN or (K > 1) lT, a code other
+ * than 0 / 1 / 3 or P >= 2^31; 5 if 64 cells beside the smallest chunk do
+ * not fit the device's free memory. */
+int bnpc_post_doublets(bnpc_post *post, const uint8_t *codes /* N x M: 0|1|3 */,
+                       int64_t M, const int32_t *labels /* N */, int64_t K,
+                       const double *theta /* K x M */, double FN, double FP,
+                       const double *logw /* K */, double lN, double lT,
+                       int64_t chunk, int64_t slab,
+                       double *own, double *ll_single, double *lse_single,
+                       double *ll_pair, double *lse_pair /* N each */,
+                       int32_t *best_single /* N */, int32_t *best_pair /* N x 2 */,
+                       double *scores /* N x P, or NULL */,
+                       double *L1, double *L0 /* P x M each, or NULL */);
+/* diagnostic: one bnpc_post_doublets call without its results' way back,
+ * milliseconds by device events summed over the call - ms[0] the uploads and
+ * the mask kernel, ms[1] the table kernel, ms[2] the sums kernel, ms[3] the
+ * per-cell reduction */
+int bnpc_post_doublets_times(bnpc_post *post, const uint8_t *codes, int64_t M,
+                             const int32_t *labels, int64_t K,
+                             const double *theta, double FN, double FP,
+                             const double *logw, double lN, double lT,
+                             int64_t chunk, int64_t slab, float *ms);
 int bnpc_post_destroy(bnpc_post *post);
 
 #ifdef __cplusplus

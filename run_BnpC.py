@@ -25,7 +25,11 @@ cell and the run's WAIC, from the log-likelihood of every cell in every
 posterior sample: cell_fit_posterior_mean.tsv, model_fit_posterior_mean.txt;
 -pm (not a reference flag either) writes how well the model explains every
 mutation and the error rates its column implies:
-mutation_fit_posterior_mean.tsv, mutation_summary_posterior_mean.txt.
+mutation_fit_posterior_mean.tsv, mutation_summary_posterior_mean.txt;
+-pd [RATE] (not a reference flag either) scores every cell against every
+cluster of the posterior clustering and every pair of them - is the cell a
+doublet? - with RATE (0.05) the prior share of doublets:
+doublets_posterior_mean.tsv, doublet_summary_posterior_mean.txt.
 """
 import argparse
 from datetime import datetime
@@ -149,6 +153,15 @@ FLAGS = [
         'false-positive rates the column implies, beside the run\'s global '
         'pair (needs -e posterior; one more pass over the samples on the '
         'GPU, over column counts per cluster).')),
+    ('output', '-pd', '--posterior_doublets', dict(type=_ratio, nargs='?',
+        const=0.05, default=argparse.SUPPRESS, metavar='RATE', help='Score '
+        'every cell against every cluster of the posterior clustering and '
+        'against every pair of them - a doublet shows the union of two '
+        'clones\' mutations - and write the best pair, the gain over the '
+        'best single cluster and the probability of a doublet per cell, with '
+        'RATE (default 0.05) the prior share of doublets (needs -e '
+        'posterior; one more pass over cells x mutations x cluster pairs on '
+        'the GPU).')),
 ]
 
 
@@ -159,6 +172,7 @@ class Args(argparse.Namespace):
     posterior_genotypes = False
     posterior_fit = False
     posterior_mutations = False
+    posterior_doublets = False
 
 
 def build_parser():
@@ -204,6 +218,10 @@ def check_args(args):
         raise SystemExit('-pm / --posterior_mutations writes tables of the '
             'posterior samples: it needs `posterior` among the estimators '
             f'(-e), which are: {" ".join(ests)}')
+    if getattr(args, 'posterior_doublets', False) and 'posterior' not in ests:
+        raise SystemExit('-pd / --posterior_doublets writes tables of the '
+            'posterior samples: it needs `posterior` among the estimators '
+            f'(-e), which are: {" ".join(ests)}')
 
 
 def save_outputs(args, results, data, out_dir, names=None):
@@ -223,7 +241,8 @@ def save_outputs(args, results, data, out_dir, names=None):
                 support=getattr(args, 'posterior_support', False),
                 cells=getattr(args, 'posterior_genotypes', False),
                 fit=getattr(args, 'posterior_fit', False),
-                mutations=getattr(args, 'posterior_mutations', False))
+                mutations=getattr(args, 'posterior_mutations', False),
+                doublets=getattr(args, 'posterior_doublets', False))
             rows_a.append(('mean', est,
                 ' '.join(str(i) for i in inf['assignment'])))
             inferred.append(('mean', est, inf))
@@ -245,6 +264,11 @@ def save_outputs(args, results, data, out_dir, names=None):
                         f'{total["FN_model"]:.4f}, FP_model '
                         f'{total["FP_model"]:.6f} (run: FN {total["FN"]:.4f}, '
                         f'FP {total["FP"]:.6f})')
+                if 'doublets' in inf:
+                    total = inf['doublets']['total']
+                    print(f'posterior doublets: {total["called"]} called, '
+                        f'{total["expected_doublets"]:.4f} expected (rate '
+                        f'{total["rate"]})')
             continue
         for chain, res in chains:
             res = res if res is not None else postproc.best_chain(results, est)
@@ -272,7 +296,8 @@ def save_outputs(args, results, data, out_dir, names=None):
             if key == 'time':
                 val = [f'{t:%Y%m%d_%H:%M:%S}' for t in val]
             if key in ('posterior_support', 'posterior_genotypes',
-                    'posterior_fit', 'posterior_mutations') and not val:
+                    'posterior_fit', 'posterior_mutations',
+                    'posterior_doublets') and not val:
                 continue        # listed only when it is set
             f.write(f'{key}: {val}\n')
     mut_names = names[1] if names is not None else None
@@ -291,6 +316,9 @@ def save_outputs(args, results, data, out_dir, names=None):
         if 'mutation_fit' in inf:
             bio.save_mutation_fit(out_dir, chain, est, inf['mutation_fit'],
                 mut_names)
+        if 'doublets' in inf:
+            bio.save_doublets(out_dir, chain, est, inf['doublets'],
+                names[0] if names is not None else None)
     # the metric tables list their rows chain by chain, as the reference
     # does (its per-chain dictionary, dpmmIO.py:524-530); the pooled
     # posterior first

@@ -37,7 +37,17 @@ trace, data and error rates, CELLS_REPS calls by device events
 (sorted), the last sample's labels (the default) and random labels: the
 fastest one's uploads and mask kernel, k_cg_rank, k_mf_count, k_mf_reduce
 beside k_cf_sums of the same run, then the call with its vectors brought to
-the host; then exit."""
+the host; then exit.
+With DOUBLETS=1 and DOUBLETS_M=<mutations> (two samples are enough: the pass
+reads none): the doublet pass (bnpc_post_doublets) for the base clustering of C
+clusters with random genotypes (a tenth of them soft), random data (30 %
+missing), DOUBLETS_CHUNK candidates and DOUBLETS_SLAB cells at a time (0: the
+defaults): DOUBLETS_REPS calls by device events (Posterior.doublets_times) -
+the fastest one's uploads and mask kernel, k_db_tables, k_db_sums,
+k_db_reduce, the (cell, candidate, mutation) steps per second of k_db_sums
+(two float64 FMAs each) beside the device's FP64 vector rate - then the call
+with its seven vectors brought to the host, and - DOUBLETS_HOST=1 - the host
+loop (postproc.host_doublets); then exit."""
 import os
 import sys
 import time
@@ -88,6 +98,54 @@ if os.environ.get('SUPPORT') == '1':
     print('  sum == 2 differ_sum:', int(differ_to.sum()) == 2 * post.differ_sum,
         '; own == 2 mpear sum:', int(differ_to[np.arange(N), labels].sum())
         == 2 * int(post.mpear_sums(labels[None])[0]))
+    post.close()
+    sys.exit(0)
+if os.environ.get('DOUBLETS') == '1':
+    # FP64 vector operations per second: 256 compute units x 4 SIMDs x 32
+    # lanes at 2.4 GHz retire one float32 operation per lane and cycle (157.3
+    # TFLOPS of FMA), a float64 one every other cycle
+    F64_OPS = 256 * 4 * 32 * 2.4e9 / 2
+    M = int(os.environ.get('DOUBLETS_M', '1000'))
+    chunk = int(os.environ.get('DOUBLETS_CHUNK', '0'))
+    slab = int(os.environ.get('DOUBLETS_SLAB', '0'))
+    reps = int(os.environ.get('DOUBLETS_REPS', '5'))
+    labels = np.unique(base, return_inverse=True)[1]
+    K = int(labels.max()) + 1
+    P = K + K * (K - 1) // 2
+    theta = (rng.random_sample((K, M)) < 0.3).astype(np.float64)
+    soft = rng.random_sample((K, M)) < 0.1
+    theta[soft] = rng.random_sample(int(soft.sum()))
+    data = (rng.random_sample((N, M)) < 0.3).astype(np.uint8)
+    data[rng.random_sample((N, M)) < 0.3] = 3
+    FN, FP = 0.2, 0.001
+    steps = N * P * M
+    print(f'doublets: M={M} K={K} P={P} chunk={chunk} slab={slab}, tables '
+        f'{P * M * 16 / 1e9:.3f} GB, scores {N * P * 8 / 1e9:.3f} GB, '
+        f'{steps:.3e} (cell, candidate, mutation) steps')
+    runs = []
+    for r in range(reps):
+        t = post.doublets_times(data, labels, theta, FN, FP, chunk=chunk,
+            slab=slab)
+        runs.append((sum(t),) + t)
+        print(f'  rep {r}: uploads + k_mf_masks {t[0] * 1e3:.3f} ms  '
+            f'k_db_tables {t[1] * 1e3:.3f} ms  k_db_sums {t[2] * 1e3:.3f} ms  '
+            f'k_db_reduce {t[3] * 1e3:.3f} ms', flush=True)
+    total, d_up, d_tab, d_sum, d_red = min(runs)
+    print(f'  fastest of {reps} (device events): pass {total * 1e3:.3f} ms; '
+        f'k_db_sums {steps / d_sum:.3e} steps/s = {2 * steps / d_sum:.3e} '
+        f'float64 FMAs/s, {2 * steps / d_sum / F64_OPS:.1%} of the FP64 '
+        f'vector rate {F64_OPS:.3e}/s', flush=True)
+    t0 = time.perf_counter()
+    got = post.doublets(data, labels, theta, FN, FP, chunk=chunk, slab=slab)
+    t0 = lap('Posterior.doublets (call, seven vectors to the host)', t0)
+    if os.environ.get('DOUBLETS_HOST') == '1':
+        want = postproc.host_doublets(data, labels, theta, FN, FP)
+        t0 = lap('host loop (postproc.host_doublets)', t0)
+        print('  best single and pair, device == host:',
+            np.array_equal(got[5], want['best_single']),
+            np.array_equal(got[6], want['best_pair']),
+            '; max |ll_pair dev - host| =',
+            float(np.abs(got[3] - want['ll_pair']).max()))
     post.close()
     sys.exit(0)
 CELLS_M = int(os.environ.get('CELLS_M', '0'))
