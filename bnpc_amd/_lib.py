@@ -331,7 +331,11 @@ SIGNATURES = {
     'bnpc_post_doublets_times': (C.c_int, [C.c_void_p, C.c_void_p, _i64,
         _pi32, _i64, _pd, C.c_double, C.c_double, _pd, C.c_double, C.c_double,
         _i64, _i64, C.POINTER(C.c_float)]),
-    'bnpc_post_ward': (C.c_int, [C.c_void_p, _pd]),
+    'bnpc_post_chain_agreement': (C.c_int, [C.c_void_p, _pi64, _i64, _pi64,
+        _pi64, _pi64]),
+    'bnpc_post_chain_agreement_times': (C.c_int, [C.c_void_p, _pi64, _i64,
+        C.c_int, C.POINTER(C.c_float)]),
+    'bnpc_post_ward':(C.c_int, [C.c_void_p, _pd]),
     'bnpc_post_ward_stats': (C.c_int, [C.c_void_p, C.POINTER(_i64),
         C.POINTER(_i64)]),
     'bnpc_post_destroy': (C.c_int, [C.c_void_p]),
@@ -990,6 +994,31 @@ class Posterior:
             theta.shape[1], ptr(labels), theta.shape[0], ptr(theta), FN, FP,
             ptr(logw), lN, lT, int(chunk), int(slab), ms),
             'post_doublets_times')
+        return tuple(x / 1e3 for x in ms)
+
+    def chain_agreement(self, bounds):
+        """Every chain against the other chains pooled (bnpc_post_chain_
+        agreement): bounds, C + 1 integers from 0 to S, chain c owns the
+        samples [bounds[c], bounds[c + 1]).  -> (abs_sum, max_abs, flips),
+        int64 (C, N) each, the integers of postproc.host_chain_agreement
+        (postproc.chain_bounds checks the bounds beforehand; the entry point
+        answers those that cannot run with code 2)."""
+        b = np.ascontiguousarray(bounds, dtype=np.int64)
+        if b.ndim != 1 or b.size < 2:
+            raise ValueError('the chain bounds must be C + 1 integers')
+        n_chains = b.size - 1
+        out = [np.empty((n_chains, self.N), dtype=np.int64) for _ in range(3)]
+        check(load().bnpc_post_chain_agreement(self._h, ptr(b), n_chains,
+            *[ptr(x) for x in out]), 'post_chain_agreement')
+        return tuple(out)
+
+    def chain_agreement_times(self, bounds, reps=5):
+        """Seconds by device events, the fastest of reps each: (the chain
+        agreement pass, one k_codist launch over the same samples)."""
+        b = np.ascontiguousarray(bounds, dtype=np.int64)
+        ms = (C.c_float * 2)()
+        check(load().bnpc_post_chain_agreement_times(self._h, ptr(b),
+            b.size - 1, int(reps), ms), 'post_chain_agreement_times')
         return tuple(x / 1e3 for x in ms)
 
     def close(self):

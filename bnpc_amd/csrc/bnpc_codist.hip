@@ -3516,3 +3516,342 @@ extern "C" int bnpc_post_doublets_times(bnpc_post *p, const uint8_t *codes,
     return db_run(p, codes, M, labels, K, theta, FN, FP, logw, lN, lT, chunk,
                   slab, out, ms);
 }
+
+// ---------------------------------------------------------------------------
+// Between-chain agreement of the clustering (-pc; not a reference output): do
+// the chains of a pooled posterior hold the same co-clustering?  The pooled
+// samples sit on the device chain after chain; bounds (C + 1 integers, 0 = b_0
+// < ... < b_C = S) say where.  With S_c = b_{c+1} - b_c, R_c = S - S_c and,
+// for a pair i != j, d_c the samples of chain c in which the two differ and
+// d = sum_c d_c the pooled count (p->differ),
+//   same_c = S_c - d_c,  same_r = (S - d) - same_c,
+//   x      = same_c R_c - same_r S_c          (x / (S_c R_c): the pair's
+//            co-clustering probability in chain c minus that in the rest)
+//   flip   = [2 same_c > S_c] != [2 same_r > R_c]
+//   abs_sum[c][i] = sum_{j != i} |x|, max_abs[c][i] = max_{j != i} |x|,
+//   flips[c][i]   = sum_{j != i} flip.
+// postproc.host_chain_agreement is the definition.  Integers only, so the
+// tables do not depend on the order of the adds or on the launch: equal bits.
+//
+// k_chain_agree is k_codist's tile loop run chain by chain: a workgroup owns a
+// 64 x 64 tile of pairs on or above the diagonal, a thread 4 x 4 counters, the
+// samples go through LDS 32 at a time and a staging round ends at the chain's
+// last sample.  The pooled counts of the tile are loaded once, into LDS (-1:
+// not a pair i < j < N; 16 more registers a thread would cost a wave per SIMD,
+// and the waves are what hides the LDS reads of the compare loop: measured
+// 1.49 x k_codist with them in registers, 1.21 x from LDS).  At a chain's end
+// the thread forms x, |x| and flip of its pairs - counts below 2^31 as 32-bit
+// operands, their products and x in 64-bit integers - and zeroes its counters:
+// the per-chain pair counts never reach memory (5 GB each at 50 000 cells).  A
+// pair adds to the row of cell i and to the column of cell j: the rows are
+// reduced over the 16 lanes that share them by shuffles, the columns over the
+// 4 rows of a wave by shuffles and over the 4 waves through LDS, and then 64 +
+// 64 consecutive threads add the tile's 128 cells into the three tables with
+// 64-bit atomics - 512 contiguous bytes per wave instruction.  One tile per
+// workgroup, as k_codist: 384 atomics per tile and chain, 9.4e8 of 8 bytes at
+// 50 000 cells x 8 chains, beside 16 compares per thread and sample.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_chain_agree(
+    const int *__restrict__ assign, long long S, long long N,
+    const int *__restrict__ differ, const long long *__restrict__ bounds,
+    int C, unsigned long long *__restrict__ abs_sum,
+    unsigned long long *__restrict__ max_abs,
+    unsigned long long *__restrict__ flips)
+{
+    const int ti = blockIdx.y, tj = blockIdx.x;
+    if (ti > tj) return;
+    __shared__ int A[SC][64];
+    __shared__ int B[SC][64];
+    __shared__ int PL[64][64];      // the tile's pooled counts
+    __shared__ unsigned long long rowres[3][64];
+    __shared__ unsigned long long colpart[4][3][64];
+    const int tid = threadIdx.x;
+    const int tx = tid & 15, ty = tid >> 4;
+    const int wave = tid >> 6;
+    int cnt[4][4];
+#pragma unroll
+    for (int a = 0; a < 4; a++) {
+        const long long i = (long long)ti * 64 + ty * 4 + a;
+#pragma unroll
+        for (int b = 0; b < 4; b++) {
+            const long long j = (long long)tj * 64 + tx * 4 + b;
+            cnt[a][b] = 0;
+            int pv = -1;
+            if (i < j && j < N)
+                pv = differ[i * (2 * N - i - 1) / 2 + (j - i - 1)];
+            PL[ty * 4 + a][tx * 4 + b] = pv;    // read back by this thread only
+        }
+    }
+
+    for (int c = 0; c < C; c++) {
+        const long long s_lo = bounds[c], s_hi = bounds[c + 1];
+        for (long long s0 = s_lo; s0 < s_hi; s0 += SC) {
+#pragma unroll
+            for (int r = 0; r < (2 * SC * 64) / 256; r++) {
+                const int e = r * 256 + tid;
+                const int which = e / (SC * 64);
+                const int rem = e - which * (SC * 64);
+                const int sc = rem >> 6, col = rem & 63;
+                const long long s = s0 + sc;
+                const long long cell = (long long)(which ? tj : ti) * 64 + col;
+                int v = -1 - col;       // padding never equals a real label
+                if (s < s_hi && cell < N) v = assign[s * N + cell];
+                if (which) B[sc][col] = v; else A[sc][col] = v;
+            }
+            __syncthreads();
+            const int lim = (s_hi - s0 < SC) ? (int)(s_hi - s0) : SC;
+            for (int sc = 0; sc < lim; sc++) {
+                const int4 av = *reinterpret_cast<const int4 *>(&A[sc][ty * 4]);
+                const int4 bv = *reinterpret_cast<const int4 *>(&B[sc][tx * 4]);
+                const int a4[4] = {av.x, av.y, av.z, av.w};
+                const int b4[4] = {bv.x, bv.y, bv.z, bv.w};
+#pragma unroll
+                for (int a = 0; a < 4; a++)
+#pragma unroll
+                    for (int b = 0; b < 4; b++)
+                        cnt[a][b] += (a4[a] != b4[b]);
+            }
+            __syncthreads();
+        }
+
+        // the chain against the rest, pair by pair
+        const unsigned St = (unsigned)S, Sc = (unsigned)(s_hi - s_lo);
+        const unsigned Rc = St - Sc;
+        // (a row at a time: its sums are reduced over the 16 lanes of one
+        // ty and stored before the next row's are formed - few live registers)
+        unsigned long long cs[4], cm[4];
+        unsigned cf[4];
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            cs[k] = cm[k] = 0;
+            cf[k] = 0;
+        }
+#pragma unroll
+        for (int a = 0; a < 4; a++) {
+            unsigned long long rs = 0, rm = 0;
+            unsigned rf = 0;
+            const int4 pv
+                = *reinterpret_cast<const int4 *>(&PL[ty * 4 + a][tx * 4]);
+            const int pooled[4] = {pv.x, pv.y, pv.z, pv.w};
+#pragma unroll
+            for (int b = 0; b < 4; b++) {
+                if (pooled[b] >= 0) {
+                    // every count is below 2^31: 32-bit operands, 64-bit
+                    // products.  same_c R_c - same_r S_c with same_r =
+                    // same - same_c is same_c S - same S_c
+                    const unsigned same_c = Sc - (unsigned)cnt[a][b];
+                    const unsigned same = St - (unsigned)pooled[b];
+                    const unsigned same_r = same - same_c;
+                    const long long x
+                        = (long long)((unsigned long long)same_c * St)
+                        - (long long)((unsigned long long)same * Sc);
+                    const unsigned long long ax
+                        = (unsigned long long)(x < 0 ? -x : x);
+                    const unsigned flip
+                        = (2u * same_c > Sc) != (2u * same_r > Rc);
+                    rs += ax;
+                    cs[b] += ax;
+                    rm = ax > rm ? ax : rm;
+                    cm[b] = ax > cm[b] ? ax : cm[b];
+                    rf += flip;
+                    cf[b] += flip;
+                }
+                cnt[a][b] = 0;
+            }
+#pragma unroll
+            for (int off = 1; off < 16; off <<= 1) {
+                const unsigned long long m = __shfl_xor(rm, off);
+                rs += __shfl_xor(rs, off);
+                rf += __shfl_xor(rf, off);
+                rm = m > rm ? m : rm;
+            }
+            if (tx == 0) {
+                rowres[0][ty * 4 + a] = rs;
+                rowres[1][ty * 4 + a] = rm;
+                rowres[2][ty * 4 + a] = rf;
+            }
+        }
+        // columns: over the 4 ty of a wave here, over the waves below
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+#pragma unroll
+            for (int off = 16; off < 64; off <<= 1) {
+                const unsigned long long m = __shfl_xor(cm[k], off);
+                cs[k] += __shfl_xor(cs[k], off);
+                cf[k] += __shfl_xor(cf[k], off);
+                cm[k] = m > cm[k] ? m : cm[k];
+            }
+        }
+        if ((tid & 63) < 16) {
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                colpart[wave][0][tx * 4 + k] = cs[k];
+                colpart[wave][1][tx * 4 + k] = cm[k];
+                colpart[wave][2][tx * 4 + k] = cf[k];
+            }
+        }
+        __syncthreads();
+        // (the next chain's staging rounds put two barriers between these
+        // reads and the next epilogue's writes: every chain has a sample)
+        if (tid < 128) {
+            const int t = tid & 63;
+            unsigned long long vs, vm, vf;
+            long long cell;
+            if (tid < 64) {
+                cell = (long long)ti * 64 + t;
+                vs = rowres[0][t];
+                vm = rowres[1][t];
+                vf = rowres[2][t];
+            } else {
+                cell = (long long)tj * 64 + t;
+                vs = vm = vf = 0;
+#pragma unroll
+                for (int w = 0; w < 4; w++) {
+                    const unsigned long long m = colpart[w][1][t];
+                    vs += colpart[w][0][t];
+                    vm = m > vm ? m : vm;
+                    vf += colpart[w][2][t];
+                }
+            }
+            if (cell < N) {
+                const size_t at = (size_t)c * N + cell;
+                if (vs) atomicAdd(&abs_sum[at], vs);
+                if (vm) atomicMax(&max_abs[at], vm);
+                if (vf) atomicAdd(&flips[at], vf);
+            }
+        }
+    }
+}
+
+// reps == 0: the pass, its tables to the host.  reps >= 1 (ms: 2 floats): no
+// output; ms[0] the fastest of reps passes (the tables' zeroing and
+// k_chain_agree), ms[1] the fastest of reps k_codist launches over the same
+// samples, which rewrite the handle's pair counts with the values they hold
+static int ca_run(bnpc_post *p, const int64_t *bounds, int64_t C,
+                  int64_t *abs_sum, int64_t *max_abs, int64_t *flips,
+                  int reps, float *ms)
+{
+    if (!p || !bounds || C < 2 || C > (int64_t)INT_MAX) {
+        bnpc_set_error("bad argument: the chain agreement needs the bounds of "
+                       "C >= 2 chains");
+        return 2;
+    }
+    const int64_t S = p->S, N = p->N;
+    if (S > (int64_t)INT_MAX) {
+        bnpc_set_error("chain agreement: %lld samples do not fit the 32-bit "
+                       "pair counts", (long long)S);
+        return 2;
+    }
+    if (bounds[0] != 0 || bounds[C] != S) {
+        bnpc_set_error("chain agreement: the bounds run from %lld to %lld, "
+                       "not from 0 to the %lld samples",
+                       (long long)bounds[0], (long long)bounds[C],
+                       (long long)S);
+        return 2;
+    }
+    for (int64_t c = 0; c < C; c++) {
+        const int64_t Sc = bounds[c + 1] - bounds[c];
+        if (Sc < 1) {
+            bnpc_set_error("chain agreement: chain %lld is empty (bounds "
+                           "%lld, %lld)", (long long)c, (long long)bounds[c],
+                           (long long)bounds[c + 1]);
+            return 2;
+        }
+    }
+    // (rising bounds from 0 to S: every chain lies inside the samples)
+    for (int64_t c = 0; c < C; c++) {
+        const int64_t Sc = bounds[c + 1] - bounds[c];
+        const unsigned __int128 span = (unsigned __int128)Sc * (S - Sc)
+            * (unsigned __int128)N * (N - 1);
+        if (span >> 63) {
+            bnpc_set_error("chain agreement: S_c R_c N (N - 1) of chain %lld "
+                           "does not fit 63 bits", (long long)c);
+            return 2;
+        }
+    }
+    PCK(hipSetDevice(p->device));
+    GtBuffers buf;
+    CgEvents evs;
+    const size_t cells = (size_t)C * N;
+    unsigned long long *d_tab = nullptr;
+    long long *d_bounds = nullptr;
+    hipError_t e = buf.alloc(&d_tab, 3 * cells);
+    if (e == hipSuccess) e = buf.alloc(&d_bounds, (size_t)C + 1);
+    if (e == hipErrorOutOfMemory) {
+        (void)hipGetLastError();
+        bnpc_set_error("chain agreement: the tables of %lld chains x %lld "
+                       "cells need %.1f GB of device memory (%s)",
+                       (long long)C, (long long)N, 24.0 * cells / 1e9,
+                       hipGetErrorString(e));
+        return 5;
+    }
+    PCK(e);
+    std::vector<long long> hb(bounds, bounds + C + 1);
+    PCK(hipMemcpy(d_bounds, hb.data(), hb.size() * sizeof(long long),
+                  hipMemcpyHostToDevice));
+    if (reps) {
+        PCK(hipEventCreate(&evs.ev[0]));
+        PCK(hipEventCreate(&evs.ev[1]));
+    }
+    const unsigned nt = (unsigned)((N + 63) / 64);
+    for (int which = 0; which < (reps ? 2 : 1); which++) {
+        for (int r = 0; r < (reps ? reps : 1); r++) {
+            if (reps) PCK(hipEventRecord(evs.ev[0], 0));
+            if (which == 0) {
+                PCK(hipMemsetAsync(d_tab, 0,
+                                   3 * cells * sizeof(unsigned long long), 0));
+                hipLaunchKernelGGL(k_chain_agree, dim3(nt, nt), dim3(256), 0,
+                                   0, p->assign, (long long)S, (long long)N,
+                                   p->differ, d_bounds, (int)C, d_tab,
+                                   d_tab + cells, d_tab + 2 * cells);
+            } else {
+                hipLaunchKernelGGL(k_codist, dim3(nt, nt), dim3(256), 0, 0,
+                                   p->assign, (long long)S, (long long)N,
+                                   p->differ);
+            }
+            PCK(hipGetLastError());
+            if (reps) {
+                float t = 0.0f;
+                PCK(hipEventRecord(evs.ev[1], 0));
+                PCK(hipEventSynchronize(evs.ev[1]));
+                PCK(hipEventElapsedTime(&t, evs.ev[0], evs.ev[1]));
+                if (r == 0 || t < ms[which]) ms[which] = t;
+            }
+        }
+    }
+    if (reps) {
+        PCK(hipDeviceSynchronize());
+        return 0;
+    }
+    // through a host copy: the outputs are written only when all is well
+    std::vector<unsigned long long> host(3 * cells);
+    PCK(hipMemcpy(host.data(), d_tab, host.size() * sizeof(unsigned long long),
+                  hipMemcpyDeviceToHost));
+    memcpy(abs_sum, host.data(), cells * sizeof(int64_t));
+    memcpy(max_abs, host.data() + cells, cells * sizeof(int64_t));
+    memcpy(flips, host.data() + 2 * cells, cells * sizeof(int64_t));
+    return 0;
+}
+
+extern "C" int bnpc_post_chain_agreement(bnpc_post *p, const int64_t *bounds,
+                                         int64_t C, int64_t *abs_sum,
+                                         int64_t *max_abs, int64_t *flips)
+{
+    if (!abs_sum || !max_abs || !flips) {
+        bnpc_set_error("bad argument: NULL");
+        return 2;
+    }
+    return ca_run(p, bounds, C, abs_sum, max_abs, flips, 0, nullptr);
+}
+
+// diagnostic (tools/posterior_bench.py): see ca_run
+extern "C" int bnpc_post_chain_agreement_times(bnpc_post *p,
+                                               const int64_t *bounds,
+                                               int64_t C, int reps, float *ms)
+{
+    if (!ms || reps < 1) {
+        bnpc_set_error("bad argument: the times need reps >= 1 and the output");
+        return 2;
+    }
+    return ca_run(p, bounds, C, nullptr, nullptr, nullptr, reps, ms);
+}

@@ -462,6 +462,58 @@ def save_doublets(out_dir, chain, est, tables, names=None):
     return paths
 
 
+def save_chain_agreement(out_dir, chain, est, tables, names=None):
+    """The -pc files of postproc.chain_agreement for one (chain, estimator)
+    row.  chain_agreement_<est>_<chain>.tsv: per cell its name (`names`, the
+    loader's cell names, when there is one per cell, else 0..N-1), `cluster`
+    (its label of assignment.txt), `worst_chain`, `worst_diff`, then per
+    chain c `diff_<c>`, `max_<c>`, `flips_<c>`; floats %.4f, flips as
+    integers.  chain_summary_<est>_<chain>.txt: `key: value` lines - chains,
+    samples (per chain), cells, pairs, per chain mean_diff, max_diff and
+    flip_share, worst_chain (the largest mean_diff, as chain:value),
+    cluster_diff (per cluster its label and the chains' values, clusters
+    separated by `;`) and unstable_cells, the ten cells with the largest
+    worst_diff (ties: the smaller index) as name:value pairs."""
+    N, C = tables['diff'].shape
+    index = np.arange(N)
+    if names is not None and np.asarray(names).size == N:
+        index = np.asarray(names)
+    index = index.tolist()
+    tag = f'{chain:0>2}'
+    paths = [os.path.join(out_dir, f'chain_agreement_{est}_{tag}.tsv'),
+        os.path.join(out_dir, f'chain_summary_{est}_{tag}.txt')]
+    with open(paths[0], 'w') as f:
+        f.write('cell\tcluster\tworst_chain\tworst_diff\t' + '\t'.join(
+            f'diff_{c}\tmax_{c}\tflips_{c}' for c in range(C)) + '\n')
+        for i, name in enumerate(index):
+            f.write(f'{name}\t{int(tables["cluster"][i])}\t'
+                f'{int(tables["worst_chain"][i])}\t'
+                f'{tables["worst_diff"][i]:.4f}\t' + '\t'.join(
+                f'{tables["diff"][i, c]:.4f}\t{tables["max_diff"][i, c]:.4f}'
+                f'\t{int(tables["flips"][i, c])}' for c in range(C)) + '\n')
+    total = tables['total']
+    worst = tables['worst_diff']
+    top = np.argsort(-worst, kind='stable')[:10]
+    with open(paths[1], 'w') as f:
+        f.write(f'chains: {total["chains"]}\n')
+        f.write('samples: ' + ' '.join(str(int(x))
+            for x in tables['samples']) + '\n')
+        f.write(f'cells: {total["cells"]}\n')
+        f.write(f'pairs: {total["pairs"]}\n')
+        for key, name in (('mean_diff_c', 'mean_diff'),
+                ('max_diff_c', 'max_diff'), ('flip_share_c', 'flip_share')):
+            f.write(f'{name}: ' + ' '.join(f'{x:.4f}'
+                for x in tables[key]) + '\n')
+        f.write(f'worst_chain: {total["worst_chain"]}:'
+            f'{total["worst_mean_diff"]:.4f}\n')
+        f.write('cluster_diff: ' + '; '.join(f'{int(k)} ' + ' '.join(
+            f'{x:.4f}' for x in row) for k, row in zip(tables['clusters'],
+            tables['cluster_diff'])) + '\n')
+        f.write('unstable_cells: ' + ' '.join(f'{index[i]}:{worst[i]:.4f}'
+            for i in top.tolist()) + '\n')
+    return paths
+
+
 def save_metric(path, column, rows):
     """V_measure.txt / ARI.txt / hammingDist.txt (dpmmIO.py:514-542): a
     tab-separated `chain  estimator  <column>` table, floats as to_csv

@@ -31,6 +31,10 @@ The -pd tables (doublet scores: every cell against every cluster of the MPEAR
 clustering and every pair of them - not a reference output) are a device pass
 over the data and the cluster genotypes (bnpc_post_doublets; host_doublets is
 the host loop it is pinned to).
+The -pc tables (every chain's co-clustering against that of the other chains
+pooled - not a reference output) are one more pass of the pair-count tile loop
+over the samples, chain by chain (bnpc_post_chain_agreement;
+host_chain_agreement is the host loop it is pinned to).
 The -tc / -td metrics (V-measure, ARI, Hamming; utils.py:49-72) are
 restated from integer counts at the end; tree helpers are out of scope.
 """
@@ -401,7 +405,7 @@ def concat_chain_results(results):
 
 
 def posterior_estimate(results, data, support=False, cells=False, fit=False,
-        mutations=False, doublets=False):
+        mutations=False, doublets=False, chains=False):
     """`-e posterior` (the default estimator), chains pooled
     (utils.py:195-244).  support=True: the key 'support' holds the tables of
     cluster_support for the MPEAR clustering, made from the pair counts of
@@ -414,7 +418,10 @@ def posterior_estimate(results, data, support=False, cells=False, fit=False,
     MPEAR clustering.  doublets: a rate in (0, 1), the prior share of
     doublets among the cells, adds the key 'doublets' with the tables of
     doublets(), made from the data, the MPEAR clustering, its genotypes and
-    the posterior means of the error rates on the same handle."""
+    the posterior means of the error rates on the same handle.  chains=True:
+    the key 'chains' holds the tables of chain_agreement, every chain's
+    samples against the other chains', with the bounds of results_bounds, on
+    the same handle."""
     res = concat_chain_results(results)
     tables = {}
     if doublets:
@@ -423,10 +430,13 @@ def posterior_estimate(results, data, support=False, cells=False, fit=False,
                 params, np.mean(res['FN']), np.mean(res['FP']), doublets)
     else:
         with_genotypes = None
-    if support or cells or fit or mutations:
+    if support or cells or fit or mutations or chains:
         def while_open(post, assign):
             if support:
                 tables['support'] = posterior_support(post, assign)
+            if chains:
+                tables['chains'] = chain_agreement(post, res['assignments'],
+                    results_bounds(results), assign)
             if cells:
                 tables['cell_genotypes'] = cell_genotypes(post,
                     res['assignments'], res['params'])
@@ -1019,6 +1029,150 @@ def doublets(post, data, labels, theta, FN, FP, rate):
 
 
 _doublet_tables = doublets      # (posterior_estimate's keyword has the name)
+
+
+# ---------------------------------------------------------------------------
+# between-chain agreement of the clustering (-pc): every chain's co-clustering
+# against that of the other chains pooled - not a reference output, so the
+# integers below are the specification
+# ---------------------------------------------------------------------------
+def chain_bounds(bounds, S, N):
+    """The bounds of C chains in S pooled samples of N cells as Python
+    integers, checked: C + 1 integers rising strictly from 0 to S (so C >= 2
+    chains, none empty), and S_c R_c N (N - 1) < 2**63 for every chain, which
+    keeps every sum of host_chain_agreement inside int64.  ValueError
+    otherwise."""
+    b = np.asarray(bounds)
+    if b.ndim != 1 or b.size < 1 or b.dtype.kind not in 'iu':
+        raise ValueError('the chain bounds must be a vector of integers')
+    b = [int(x) for x in b.tolist()]
+    C = len(b) - 1
+    if C < 2:
+        raise ValueError(f'the chain agreement compares chains: {C} chain '
+            'has no others (it needs C >= 2)')
+    if b[0] != 0 or b[-1] != S:
+        raise ValueError(f'the chain bounds run from {b[0]} to {b[-1]}, not '
+            f'from 0 to the {S} samples')
+    for c in range(C):
+        if b[c + 1] <= b[c]:
+            raise ValueError(f'chain {c} is empty: the bounds {b[c]}, '
+                f'{b[c + 1]} do not increase')
+        Sc = b[c + 1] - b[c]
+        if Sc * (S - Sc) * N * (N - 1) >= 2 ** 63:
+            raise ValueError(f'S_c R_c N (N - 1) of chain {c} does not fit '
+                '63 bits')
+    return b
+
+
+def host_chain_agreement(assignments, bounds):
+    """(abs_sum, max_abs, flips), int64 (C, N) each - the definition the
+    device pass (bnpc_post_chain_agreement) is pinned to.  assignments: the
+    pooled S x N samples; chain c owns the samples [bounds[c], bounds[c + 1]).
+    With S_c its length, R_c = S - S_c and, for cells i != j, d_c the samples
+    of chain c in which they differ in label and d = sum_c d_c:
+      same_c = S_c - d_c,  same_r = (S - d) - same_c
+      x      = same_c R_c - same_r S_c  (x / (S_c R_c): the pair's
+               co-clustering probability in chain c minus that in the rest)
+      flip   = [2 same_c > S_c] != [2 same_r > R_c]  (exactly half: apart)
+      abs_sum[c][i] = sum_{j != i} |x|, max_abs[c][i] = max_{j != i} |x|,
+      flips[c][i] = sum_{j != i} flip.
+    Row by row: a chain's samples against one cell's column at a time."""
+    a = np.asarray(assignments)
+    if a.ndim != 2:
+        raise ValueError('the samples must be samples x cells')
+    S, N = a.shape
+    b = chain_bounds(bounds, S, N)
+    C = len(b) - 1
+    Sc = np.diff(np.array(b, dtype=np.int64))
+    Rc = S - Sc
+    abs_sum = np.zeros((C, N), dtype=np.int64)
+    max_abs = np.zeros((C, N), dtype=np.int64)
+    flips = np.zeros((C, N), dtype=np.int64)
+    others = np.ones(N, dtype=bool)
+    for i in range(N):
+        d_c = np.stack([np.count_nonzero(
+            a[b[c]:b[c + 1]] != a[b[c]:b[c + 1], i:i + 1], axis=0)
+            for c in range(C)]).astype(np.int64)            # C x N
+        same_c = Sc[:, None] - d_c
+        same_r = (S - d_c.sum(axis=0))[None, :] - same_c
+        x = np.abs(same_c * Rc[:, None] - same_r * Sc[:, None])
+        flip = (2 * same_c > Sc[:, None]) != (2 * same_r > Rc[:, None])
+        others[i] = False
+        if N > 1:
+            abs_sum[:, i] = x[:, others].sum(axis=1)
+            max_abs[:, i] = x[:, others].max(axis=1)
+            flips[:, i] = flip[:, others].sum(axis=1)
+        others[i] = True
+    return abs_sum, max_abs, flips
+
+
+def chain_agreement(post, assignments, bounds, labels):
+    """The -pc tables: did the chains find the same clustering?  From the
+    integers of host_chain_agreement - the device pass
+    (Posterior.chain_agreement) where the open clustering handle has one, else
+    the host loop on the samples - in float64, the same arithmetic either
+    way.  Per cell and chain, (N, C): 'diff' = abs_sum / (S_c R_c (N - 1)), the
+    mean absolute difference between the co-clustering probabilities of the
+    cell's pairs in chain c and in the other chains; 'max_diff' = max_abs /
+    (S_c R_c); 'flips' (integers) and 'flip_share' = flips / (N - 1), the
+    pairs the two sides call differently at 0.5.  Per cell: 'cluster' (labels,
+    the MPEAR clustering), 'worst_chain' (the largest diff, ties: the smallest
+    index) and 'worst_diff'.  Per chain, (C,): 'samples', 'mean_diff_c' =
+    (sum_i abs_sum) / (S_c R_c N (N - 1)) with the integer sum taken first,
+    'max_diff_c', 'flip_share_c' = sum_i flips / (N (N - 1)).  'clusters' (the
+    sorted labels) and 'cluster_diff' (clusters x chains): the mean diff of a
+    cluster's cells.  'total': {'chains', 'cells', 'pairs', 'samples',
+    'mean_diff' (the mean of the chains'), 'worst_chain', 'worst_mean_diff',
+    'flip_share' (all chains pooled)}."""
+    a = np.asarray(assignments)
+    S, N = a.shape
+    b = chain_bounds(bounds, S, N)
+    C = len(b) - 1
+    device = getattr(post, 'chain_agreement', None)
+    if device is not None:
+        abs_sum, max_abs, flips = device(np.array(b, dtype=np.int64))
+    else:
+        abs_sum, max_abs, flips = host_chain_agreement(a, b)
+    abs_sum, max_abs, flips = (np.asarray(x, dtype=np.int64)
+        for x in (abs_sum, max_abs, flips))
+    labels = np.asarray(labels)
+    Sc = [b[c + 1] - b[c] for c in range(C)]
+    span = [Sc[c] * (S - Sc[c]) for c in range(C)]          # S_c R_c, exact
+    diff = np.empty((N, C))
+    max_diff = np.empty((N, C))
+    for c in range(C):
+        diff[:, c] = abs_sum[c] / float(span[c] * (N - 1))
+        max_diff[:, c] = max_abs[c] / float(span[c])
+    flip_share = flips.T / float(N - 1)
+    worst = np.argmax(diff, axis=1).astype(np.int64)
+    mean_diff_c = np.array([sum(abs_sum[c].tolist())
+        / (span[c] * N * (N - 1)) for c in range(C)])
+    flip_share_c = np.array([sum(flips[c].tolist()) / (N * (N - 1))
+        for c in range(C)])
+    clusters = np.unique(labels)
+    cluster_diff = np.array([diff[labels == k].mean(axis=0)
+        for k in clusters]).reshape(clusters.size, C)
+    worst_c = int(np.argmax(mean_diff_c))
+    return {'cluster': labels, 'worst_chain': worst,
+        'worst_diff': diff[np.arange(N), worst], 'diff': diff,
+        'max_diff': max_diff, 'flips': np.ascontiguousarray(flips.T),
+        'flip_share': flip_share,
+        'samples': np.array(Sc, dtype=np.int64), 'mean_diff_c': mean_diff_c,
+        'max_diff_c': max_diff.max(axis=0), 'flip_share_c': flip_share_c,
+        'clusters': clusters, 'cluster_diff': cluster_diff,
+        'total': {'chains': C, 'cells': int(N), 'pairs': N * (N - 1) // 2,
+            'samples': int(S), 'mean_diff': float(mean_diff_c.mean()),
+            'worst_chain': worst_c,
+            'worst_mean_diff': float(mean_diff_c[worst_c]),
+            'flip_share': sum(flips.ravel().tolist())
+                / (C * N * (N - 1))}}
+
+
+def results_bounds(results):
+    """The bounds of the chains in concat_chain_results' pooled samples:
+    every chain's post-burn-in length, in the order of results."""
+    return np.concatenate([[0], np.cumsum([len(r['assignments'])
+        - int(r['burn_in']) for r in results])]).astype(np.int64)
 
 
 # ---------------------------------------------------------------------------

@@ -1212,6 +1212,34 @@ int bnpc_post_doublets_times(bnpc_post *post, const uint8_t *codes, int64_t M,
                              const double *theta, double FN, double FP,
                              const double *logw, double lN, double lT,
                              int64_t chunk, int64_t slab, float *ms);
+/* Between-chain agreement of the clustering (-pc; not a reference output): is
+ * one chain's co-clustering that of the others?  The post's samples are the
+ * chains' pooled samples, chain after chain; bounds (C + 1 int64, 0 = b_0 <
+ * b_1 < ... < b_C = S) gives chain c the samples [b_c, b_{c+1}).  With S_c =
+ * b_{c+1} - b_c, R_c = S - S_c, d_c the samples of chain c in which cells
+ * i != j differ and d the pooled count of the pair,
+ *   same_c = S_c - d_c,  same_r = (S - d) - same_c,
+ *   x = same_c R_c - same_r S_c,
+ *   flip = [2 same_c > S_c] != [2 same_r > R_c],
+ * the three C x N int64 tables (row-major) are
+ *   abs_sum[c][i] = sum over j != i of |x|,  max_abs[c][i] = max of |x|,
+ *   flips[c][i] = sum of flip
+ * (bnpc_amd.postproc.host_chain_agreement is the definition).  One kernel:
+ * the pair counts' tile loop chain by chain, integers only, 64-bit atomics
+ * into the tables - the same bits on every call; no per-chain matrix of pair
+ * counts is made.  Return code 2, and no output written, for C < 2, an empty
+ * chain, bounds that do not rise strictly from 0 to S, or S_c R_c N (N - 1)
+ * >= 2^63 for some chain; 5 if the tables do not fit the device's free
+ * memory. */
+int bnpc_post_chain_agreement(bnpc_post *post, const int64_t *bounds, int64_t C,
+                              int64_t *abs_sum, int64_t *max_abs,
+                              int64_t *flips /* C x N each */);
+/* diagnostic: milliseconds by device events, the fastest of reps each -
+ * ms[0] the pass above (the tables' zeroing and its kernel), ms[1] one launch
+ * of the pair-count kernel of bnpc_post_create over the same samples (it
+ * rewrites the post's pair counts with the values they hold) */
+int bnpc_post_chain_agreement_times(bnpc_post *post, const int64_t *bounds,
+                                    int64_t C, int reps, float *ms);
 int bnpc_post_destroy(bnpc_post *post);
 
 #ifdef __cplusplus

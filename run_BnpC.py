@@ -29,7 +29,11 @@ mutation_fit_posterior_mean.tsv, mutation_summary_posterior_mean.txt;
 -pd [RATE] (not a reference flag either) scores every cell against every
 cluster of the posterior clustering and every pair of them - is the cell a
 doublet? - with RATE (0.05) the prior share of doublets:
-doublets_posterior_mean.tsv, doublet_summary_posterior_mean.txt.
+doublets_posterior_mean.tsv, doublet_summary_posterior_mean.txt;
+-pc (not a reference flag either) compares every chain's co-clustering with
+that of the other chains pooled - did the chains find the same clustering?
+(needs -n 2 or more): chain_agreement_posterior_mean.tsv,
+chain_summary_posterior_mean.txt.
 """
 import argparse
 from datetime import datetime
@@ -162,6 +166,13 @@ FLAGS = [
         'RATE (default 0.05) the prior share of doublets (needs -e '
         'posterior; one more pass over cells x mutations x cluster pairs on '
         'the GPU).')),
+    ('output', '-pc', '--posterior_chains', dict(action='store_true',
+        default=argparse.SUPPRESS, help='Compare the posterior co-clustering '
+        'of every chain with that of the other chains pooled and write, per '
+        'cell and chain, the mean and the largest difference and the pairs '
+        'the two sides call differently: a chain that stands out has not '
+        'mixed (needs -e posterior and -n 2 or more; one more pass over '
+        'samples x pairs of cells on the GPU).')),
 ]
 
 
@@ -173,6 +184,7 @@ class Args(argparse.Namespace):
     posterior_fit = False
     posterior_mutations = False
     posterior_doublets = False
+    posterior_chains = False
 
 
 def build_parser():
@@ -222,6 +234,18 @@ def check_args(args):
         raise SystemExit('-pd / --posterior_doublets writes tables of the '
             'posterior samples: it needs `posterior` among the estimators '
             f'(-e), which are: {" ".join(ests)}')
+    if getattr(args, 'posterior_chains', False):
+        if 'posterior' not in ests:
+            raise SystemExit('-pc / --posterior_chains writes tables of the '
+                'posterior samples: it needs `posterior` among the estimators '
+                f'(-e), which are: {" ".join(ests)}')
+        if getattr(args, 'debug', False):
+            raise SystemExit('-pc / --posterior_chains compares chains with '
+                'each other: --debug runs a single chain')
+        if getattr(args, 'chains', 1) < 2:
+            raise SystemExit('-pc / --posterior_chains compares chains with '
+                'each other: it needs two or more (-n), not '
+                f'{getattr(args, "chains", 1)}')
 
 
 def save_outputs(args, results, data, out_dir, names=None):
@@ -242,7 +266,8 @@ def save_outputs(args, results, data, out_dir, names=None):
                 cells=getattr(args, 'posterior_genotypes', False),
                 fit=getattr(args, 'posterior_fit', False),
                 mutations=getattr(args, 'posterior_mutations', False),
-                doublets=getattr(args, 'posterior_doublets', False))
+                doublets=getattr(args, 'posterior_doublets', False),
+                chains=getattr(args, 'posterior_chains', False))
             rows_a.append(('mean', est,
                 ' '.join(str(i) for i in inf['assignment'])))
             inferred.append(('mean', est, inf))
@@ -269,6 +294,13 @@ def save_outputs(args, results, data, out_dir, names=None):
                     print(f'posterior doublets: {total["called"]} called, '
                         f'{total["expected_doublets"]:.4f} expected (rate '
                         f'{total["rate"]})')
+                if 'chains' in inf:
+                    total = inf['chains']['total']
+                    print('posterior chains: mean difference '
+                        f'{total["mean_diff"]:.4f}, worst chain '
+                        f'{total["worst_chain"]} '
+                        f'({total["worst_mean_diff"]:.4f}), flip share '
+                        f'{total["flip_share"]:.4f}')
             continue
         for chain, res in chains:
             res = res if res is not None else postproc.best_chain(results, est)
@@ -297,7 +329,7 @@ def save_outputs(args, results, data, out_dir, names=None):
                 val = [f'{t:%Y%m%d_%H:%M:%S}' for t in val]
             if key in ('posterior_support', 'posterior_genotypes',
                     'posterior_fit', 'posterior_mutations',
-                    'posterior_doublets') and not val:
+                    'posterior_doublets', 'posterior_chains') and not val:
                 continue        # listed only when it is set
             f.write(f'{key}: {val}\n')
     mut_names = names[1] if names is not None else None
@@ -318,6 +350,9 @@ def save_outputs(args, results, data, out_dir, names=None):
                 mut_names)
         if 'doublets' in inf:
             bio.save_doublets(out_dir, chain, est, inf['doublets'],
+                names[0] if names is not None else None)
+        if 'chains' in inf:
+            bio.save_chain_agreement(out_dir, chain, est, inf['chains'],
                 names[0] if names is not None else None)
     # the metric tables list their rows chain by chain, as the reference
     # does (its per-chain dictionary, dpmmIO.py:524-530); the pooled

@@ -47,7 +47,16 @@ the fastest one's uploads and mask kernel, k_db_tables, k_db_sums,
 k_db_reduce, the (cell, candidate, mutation) steps per second of k_db_sums
 (two float64 FMAs each) beside the device's FP64 vector rate - then the call
 with its seven vectors brought to the host, and - DOUBLETS_HOST=1 - the host
-loop (postproc.host_doublets); then exit."""
+loop (postproc.host_doublets); then exit.
+CHAINS=<C>: right after the pair counts are made, the between-chain agreement
+pass (bnpc_post_chain_agreement) with the S samples cut into C chains of equal
+length (the first S mod C one longer): the pass - the tables' zeroing and
+k_chain_agree - beside one k_codist launch over the same samples, by device
+events, the fastest of CHAINS_REPS (default 5) each
+(Posterior.chain_agreement_times), the label compares per second of both and
+the atomics the pass issues at most; then the call with its three tables
+brought to the host and - CHAINS_HOST=1 - the host loop
+(postproc.host_chain_agreement) compared with it; then exit."""
 import os
 import sys
 import time
@@ -98,6 +107,35 @@ if os.environ.get('SUPPORT') == '1':
     print('  sum == 2 differ_sum:', int(differ_to.sum()) == 2 * post.differ_sum,
         '; own == 2 mpear sum:', int(differ_to[np.arange(N), labels].sum())
         == 2 * int(post.mpear_sums(labels[None])[0]))
+    post.close()
+    sys.exit(0)
+if os.environ.get('CHAINS'):
+    n_chains = int(os.environ['CHAINS'])
+    reps = int(os.environ.get('CHAINS_REPS', '5'))
+    lengths = np.full(n_chains, S // n_chains)
+    lengths[:S % n_chains] += 1
+    bounds = np.concatenate([[0], np.cumsum(lengths)]).astype(np.int64)
+    compares = S * N * (N - 1) // 2
+    tiles = ((N + 63) // 64) * ((N + 63) // 64 + 1) // 2
+    t_pass, t_codist = post.chain_agreement_times(bounds, reps)
+    print(f'chain agreement: {n_chains} chains of {lengths.min()}..'
+        f'{lengths.max()} samples, {compares:.3e} label compares, at most '
+        f'{384 * tiles * n_chains:.3e} 64-bit atomics, tables '
+        f'{24 * n_chains * N / 1e6:.2f} MB (device events, fastest of '
+        f'{reps}):')
+    for name, t in (('k_chain_agree + zeroing', t_pass),
+            ('k_codist', t_codist)):
+        print(f'    {name:32s} {t * 1e3:9.3f} ms  {compares / t:.3e} '
+            'compares/s', flush=True)
+    print(f'    pass / k_codist time: {t_pass / t_codist:.3f}x')
+    t0 = time.perf_counter()
+    got = post.chain_agreement(bounds)
+    t0 = lap('Posterior.chain_agreement (call, three tables to the host)', t0)
+    if os.environ.get('CHAINS_HOST') == '1':
+        want = postproc.host_chain_agreement(a, bounds)
+        t0 = lap('host loop (postproc.host_chain_agreement)', t0)
+        print('  device == host:', all(np.array_equal(g, w)
+            for g, w in zip(got, want)))
     post.close()
     sys.exit(0)
 if os.environ.get('DOUBLETS') == '1':
