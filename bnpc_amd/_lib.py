@@ -38,12 +38,12 @@ MAX_TRIALS = 4
 HINT_COLS_MAX = 32767   # columns of a hinted sweep (bnpc_top2 holds them as int16)
 SUPPORT_KC = 128    # include/bnpc_hip.h: BNPC_SUPPORT_KC (clusters per pass)
 # the most cells whose rank pass (bnpc_post_cell_genotypes) works in LDS:
-# bnpc_codist.hip, 8 ceil(N / 32) + 1040 bytes <= CG_LDS_MAX = 65536
+# bnpc_post_passes.hip, 8 ceil(N / 32) + 1040 bytes <= CG_LDS_MAX = 65536
 CELL_RANK_LDS_CELLS = 257984
-CELL_TILE = 8       # bnpc_codist.hip: CG_CELLS (cells per workgroup)
-MUT_FIT_ROWS = 32   # bnpc_codist.hip: MF_ROWS (cluster rows of a wave's LDS tile)
-DOUBLET_TILE = 8    # bnpc_codist.hip: DB_TILE (candidates of a wave of k_db_sums)
-DOUBLET_UNROLL = 2  # bnpc_codist.hip: DB_UNROLL (mutations per trip of its loop)
+CELL_TILE = 8       # bnpc_post_passes.hip: CG_CELLS (cells per workgroup)
+MUT_FIT_ROWS = 32   # bnpc_post_passes.hip: MF_ROWS (cluster rows of a wave's LDS tile)
+DOUBLET_TILE = 8    # bnpc_post_passes.hip: DB_TILE (candidates of a wave of k_db_sums)
+DOUBLET_UNROLL = 2  # bnpc_post_passes.hip: DB_UNROLL (mutations per trip of its loop)
 
 _i64 = C.c_int64
 # array arguments travel as plain addresses (building a typed ctypes pointer

@@ -16,10 +16,12 @@ SOURCES = [os.path.join(PKG, 'csrc', 'bnpc_kernels.hip'),
     os.path.join(PKG, 'csrc', 'bnpc_hostmath.cpp'),
     os.path.join(PKG, 'csrc', 'bnpc_mt.cpp'),
     os.path.join(PKG, 'csrc', 'bnpc_ingest.cpp'),
-    os.path.join(PKG, 'csrc', 'bnpc_codist.hip')]
+    os.path.join(PKG, 'csrc', 'bnpc_codist.hip'),
+    os.path.join(PKG, 'csrc', 'bnpc_post_passes.hip')]
 HEADERS = [os.path.join(ROOT, 'include', 'bnpc_hip.h'),
     os.path.join(PKG, 'csrc', 'bnpc_internal.h'),
-    os.path.join(PKG, 'csrc', 'bnpc_ctx.h')]
+    os.path.join(PKG, 'csrc', 'bnpc_ctx.h'),
+    os.path.join(PKG, 'csrc', 'bnpc_post.h')]
 TARGET = os.path.join(PKG, 'libbnpc_hip.so')
 # BNPC_SANITIZE=thread|address,undefined builds the HOST side instrumented
 # into build/libbnpc_hip.<sanitizer>.so (git- AND gpurun-ignored: CPU runs

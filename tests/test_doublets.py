@@ -561,7 +561,7 @@ def test_binding_and_header_list_the_entry_points():
         r'const uint8_t \*codes', header)
     assert re.search(r'\bint bnpc_post_doublets_times\(bnpc_post \*post',
         header)
-    with open(os.path.join(ROOT, 'bnpc_amd', 'csrc', 'bnpc_codist.hip')) as f:
+    with open(os.path.join(ROOT, 'bnpc_amd', 'csrc', 'bnpc_post_passes.hip')) as f:
         source = f.read()
     assert f'#define DB_TILE {_lib.DOUBLET_TILE} ' in source
     assert f'#define DB_UNROLL {_lib.DOUBLET_UNROLL} ' in source

@@ -432,7 +432,7 @@ def test_binding_and_header_list_the_entry_points():
         r'const uint8_t \*codes', header)
     assert re.search(r'\bint bnpc_post_mutation_fit_times\(bnpc_post \*post',
         header)
-    with open(os.path.join(ROOT, 'bnpc_amd', 'csrc', 'bnpc_codist.hip')) as f:
+    with open(os.path.join(ROOT, 'bnpc_amd', 'csrc', 'bnpc_post_passes.hip')) as f:
         source = f.read()
     assert f'#define MF_ROWS {_lib.MUT_FIT_ROWS} ' in source
     assert _lib.ABI_VERSION == 12

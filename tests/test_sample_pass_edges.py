@@ -1,4 +1,4 @@
-"""The posterior sample passes of bnpc_codist.hip (bnpc_post_genotypes, -pg
+"""The posterior sample passes of bnpc_post_passes.hip (bnpc_post_genotypes, -pg
 and -pf with the rank pass they share) at the edges their feature tests do
 not enter, against the host loops they are pinned to (postproc.host_genotypes,
 host_cell_genotypes, host_cell_fit).  array_equal wherever the sibling files
@@ -55,9 +55,9 @@ import test_cell_genotypes_gpu as CG
 import test_genotypes_gpu as G
 
 ULP = 2.0 ** -52
-GRID_MAX = 65535        # bnpc_codist.hip: the most workgroups of a sample loop
-CG_LDS_MAX = 65536      # bnpc_codist.hip: the rank pass's LDS limit, bytes
-GT_LDS_MAX = 163840     # bnpc_codist.hip: the genotype passes' LDS limit
+GRID_MAX = 65535        # bnpc_post.h: the most workgroups of a sample loop
+CG_LDS_MAX = 65536      # bnpc_post_passes.hip: the rank pass's LDS limit, bytes
+GT_LDS_MAX = 163840     # bnpc_post_passes.hip: the genotype passes' LDS limit
 S_WRAP = GRID_MAX + 3
 
 
