@@ -17,6 +17,7 @@ SOURCES = [os.path.join(PKG, 'csrc', 'bnpc_kernels.hip'),
     os.path.join(PKG, 'csrc', 'bnpc_mt.cpp'),
     os.path.join(PKG, 'csrc', 'bnpc_ingest.cpp'),
     os.path.join(PKG, 'csrc', 'bnpc_codist.hip'),
+    os.path.join(PKG, 'csrc', 'bnpc_post_ward.hip'),
     os.path.join(PKG, 'csrc', 'bnpc_post_passes.hip')]
 HEADERS = [os.path.join(ROOT, 'include', 'bnpc_hip.h'),
     os.path.join(PKG, 'csrc', 'bnpc_internal.h'),

@@ -1,12 +1,15 @@
 // bnpc_post.h - the posterior handle and the host-side pieces every posterior
-// pass's driver is made of.  Internal to bnpc_codist.hip (the passes over the
-// labels and the pair counts) and bnpc_post_passes.hip (the passes over the
+// pass's driver is made of.  Internal to bnpc_codist.hip (the handle and the
+// passes over the labels and the pair counts), bnpc_post_ward.hip (Ward's
+// linkage of the pair counts) and bnpc_post_passes.hip (the passes over the
 // parameter trace or the data).
 //
 // No kernel is declared here: a kernel is launched only from the translation
 // unit that defines it, so the two helpers that launch one
 // (post_check_distinct: k_cg_rank, post_build_masks: k_mf_masks) stand beside
-// their kernels in bnpc_post_passes.hip.
+// their kernels in bnpc_post_passes.hip.  What one file alone holds stays in
+// that file too: the handle's owner while it is made (bnpc_codist.hip), the
+// holder of Ward's stream and captured graph (bnpc_post_ward.hip).
 //
 // What every driver keeps, whatever it shares:
 //   - the order of its checks: the arguments (code 2), the handle's labels,

@@ -1,5 +1,5 @@
-"""The posterior estimator's device kernels (bnpc_amd/csrc/bnpc_codist.hip) at
-the forms and edges a real workload takes and tests/test_posterior.py does
+"""The posterior estimator's device kernels (bnpc_amd/csrc/bnpc_codist.hip and,
+for the Ward linkage, bnpc_amd/csrc/bnpc_post_ward.hip) at the forms and edges a real workload takes and tests/test_posterior.py does
 not: k_codist's 32-sample rounds and 64 x 64 tiles, the 64 Mi-element slabs of
 bnpc_post_fetch, a sum of pair counts past 2^32, k_mpear_sums with several
 tiles per workgroup and every candidate chunking, and the Ward linkage at its
