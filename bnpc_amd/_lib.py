@@ -1357,7 +1357,8 @@ def rows_copy_zero(dst, src=None):
 
 def mh_batch(kernels, old, n1, n0, sd, tmin, tmax, FP, FN, p, q, uniform,
             trans_prob, known=None, want_prior=False, draws=None,
-            threads=None, ctx=None, counts_src=0, label=None):
+            threads=None, ctx=None, counts_src=0, label=None,
+            prior_seq_sum=None):
     """bnpc_mh_batch: the draws and the arithmetic of MH_cluster_params for
     the G rows of `old` (float32 G x M).  `draws` = (sd_idx, U, u) evaluates
     given draws instead of taking them from the global stream.  With `ctx`
@@ -1366,6 +1367,9 @@ def mh_batch(kernels, old, n1, n0, sd, tmin, tmax, FP, FN, p, q, uniform,
     first and the host evaluates only what it leaves (bnpc_mh_batch_dev);
     with `label` = (assignment, ids) the per-cluster counts are made in the
     same call and n1 / n0 RECEIVE them (bnpc_label_counts_and_batch).
+    `prior_seq_sum` (a float64 array of one element, NaN or a value to
+    continue from) receives the sum of the prior densities in index order
+    where the batch is screened (bnpc_mh_args.prior_seq_sum).
     Returns (status, new, log_prob, declined, prior, (sd_idx, U, u)); status
     1: only the draws are valid - they are views of scratch that the next
     call overwrites."""
@@ -1400,6 +1404,11 @@ def mh_batch(kernels, old, n1, n0, sd, tmin, tmax, FP, FN, p, q, uniform,
     a.log_prob, a.declined = ptr(log_prob), ptr(declined)
     a.threads = threads_for(G * M) if threads is None else threads
     a.screen = None
+    if prior_seq_sum is not None:
+        assert prior_seq_sum.dtype == np.float64 and prior_seq_sum.size == 1 \
+            and prior_seq_sum.flags['C_CONTIGUOUS']
+    a.prior_seq_sum = ptr(prior_seq_sum) if prior_seq_sum is not None \
+        else None
     status = C.c_int(0)
     lib = load()
     handle = getattr(ctx, '_h', None)
@@ -1477,6 +1486,7 @@ def rg_scan_step(ctx, kernels, view, n, rg_assignment, DP_a, theta3, sd, tmin,
     a.uniform_prior = int(bool(uniform))
     a.trans_prob = int(bool(trans_prob))
     a.known_theta = a.known_prior = a.prior_out = None
+    a.prior_seq_sum = None      # (the block is shared with mh_batch)
     a.new_theta = ptr(new)
     a.log_prob, a.declined = ptr(log_prob), ptr(declined)
     a.threads = threads_for(G * M) if threads is None else threads

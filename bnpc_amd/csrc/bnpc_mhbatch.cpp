@@ -408,12 +408,34 @@ static int mh_batch_dev_impl(bnpc_ctx *c, const bnpc_host_kernels *k,
                 if (int rc = mh_batch_dev_impl(c, k, rng, &b, 0, &st, nullptr,
                                                g0, a->G))
                     return rc;
-                // (an element left to SciPy: the caller puts the stream back
-                // and walks the whole batch by the binding - no point in
-                // going on)
+                // (an element left to SciPy: the caller evaluates the whole
+                // batch from its draws - no point in going on.  Status 1
+                // promises ALL the draws and the stream behind them: the
+                // rows of the slices not reached are drawn here, straight
+                // into the caller's arrays)
                 if (st) {
                     *status = 1;
+                    const int64_t done = g0 + Gs;
+                    if (rng && done < a->G) {
+                        const size_t rest = (size_t)done * a->M;
+                        if (int rc = bnpc_mt_mh_draws(rng, a->G - done, a->M,
+                                a->n_sd, a->sd_idx + rest, a->U + rest,
+                                a->u + rest))
+                            return rc;
+                    }
                     return 0;
+                }
+                // (a last slice below the screen's minimum went to the plain
+                // batch, which keeps no sum of the densities: continued here,
+                // one accumulator, index order)
+                if (b.prior_seq_sum && b.prior_out && !a->uniform_prior
+                    && !mh_screen_applies(c, &b)) {
+                    const size_t n = (size_t)Gs * a->M;
+                    double s = *b.prior_seq_sum;
+                    size_t i = 0;
+                    if (s != s) s = b.prior_out[i++];
+                    for (; i < n; i++) s += b.prior_out[i];
+                    *b.prior_seq_sum = s;
                 }
             }
             return 0;
@@ -719,9 +741,11 @@ static int mh_batch_dev_impl(bnpc_ctx *c, const bnpc_host_kernels *k,
                         us(ts0, t_issued[p]), t_draws_us[p], us(ts0, t_got[p]),
                         us(ts0, t_waited[p]), us(ts0, t_hosted[p]));
     }
-    if (*status != 0) {
+    if (*status != 0 || (rng && G_all >= 0)) {
         // the caller's view of the draws (the SciPy-level twin evaluates the
-        // batch from them when the library hands an element back)
+        // batch from them when the library hands an element back; a slice's
+        // are taken out before the next slice reuses the block - a later one
+        // may be the one that hands the batch back)
         memcpy(a->sd_idx, h.sd_idx, E * 4);
         memcpy(a->U, h.U, E * 8);
         memcpy(a->u, h.u, E * 8);

@@ -557,8 +557,12 @@ int bnpc_mh_screen(bnpc_ctx *ctx, int counts_src, const bnpc_mh_args *a,
  * counts, the host evaluates what is left (a few per cent) exactly as
  * bnpc_mh_batch does - same results bit for bit, a tenth of the host work.
  * Scored batches (trans_prob), small ones and BNPC_MH_SCREEN=0 go to
- * bnpc_mh_batch directly.  On return the caller's sd_idx / U / u hold the
- * draws. */
+ * bnpc_mh_batch directly.  With *status = 1 the caller's sd_idx / U / u hold
+ * ALL the draws of the batch and the stream stands behind them, as after
+ * bnpc_mh_batch; a screened batch that ends with *status = 0 keeps its draws
+ * in the pinned block and hands none back (a batch screened in slices of
+ * rows, beyond the pinned budget, hands back those of the slices it
+ * screened). */
 int bnpc_mh_batch_dev(bnpc_ctx *ctx, const bnpc_host_kernels *k,
                       bnpc_mt19937 *rng, const bnpc_mh_args *a,
                       int counts_src, int *status);
