@@ -331,6 +331,12 @@ SIGNATURES = {
     'bnpc_post_doublets_times': (C.c_int, [C.c_void_p, C.c_void_p, _i64,
         _pi32, _i64, _pd, C.c_double, C.c_double, _pd, C.c_double, C.c_double,
         _i64, _i64, C.POINTER(C.c_float)]),
+    'bnpc_post_place': (C.c_int, [C.c_void_p, C.c_void_p, _i64, _i64, _pi32,
+        _i64, _pf, _i64, _pd, _pd, _pd, C.c_double, C.c_double, _i64, _i64,
+        _pd, _pd, _pd, _pd, _pd, _pd]),
+    'bnpc_post_place_times': (C.c_int, [C.c_void_p, C.c_void_p, _i64, _i64,
+        _pi32, _i64, _pf, _i64, _pd, _pd, _pd, C.c_double, C.c_double, _i64,
+        _i64, C.POINTER(C.c_float)]),
     'bnpc_post_chain_agreement': (C.c_int, [C.c_void_p, _pi64, _i64, _pi64,
         _pi64, _pi64]),
     'bnpc_post_chain_agreement_times': (C.c_int, [C.c_void_p, _pi64, _i64,
@@ -994,6 +1000,81 @@ class Posterior:
             theta.shape[1], ptr(labels), theta.shape[0], ptr(theta), FN, FP,
             ptr(logw), lN, lT, int(chunk), int(slab), ms),
             'post_doublets_times')
+        return tuple(x / 1e3 for x in ms)
+
+    def _place_args(self, new_data, labels, params, FN, FP, alpha, prior):
+        par = self._trace(params)
+        codes = data_codes(new_data)
+        if codes.ndim != 2 or codes.shape[0] < 1 \
+                or codes.shape[1] != par.shape[2]:
+            raise ValueError('the new cells must be Q >= 1 cells x the '
+                f'{par.shape[2]} mutations of the trace, not {codes.shape}')
+        labels = np.ascontiguousarray(labels, dtype=np.int32)
+        if labels.shape != (self.N,):
+            raise ValueError(f'the clustering must hold {self.N} labels')
+        K = int(labels.max()) + 1 if labels.size else 0
+        rates = [np.ascontiguousarray(x, dtype=np.float64)
+            for x in (FN, FP, alpha)]
+        if any(x.shape != (self.S,) for x in rates):
+            raise ValueError(f'FN, FP and alpha must hold {self.S} samples '
+                'each')
+        p, q = (float(x) for x in prior)
+        return codes, labels, K, par, rates, p / (p + q), q / (p + q)
+
+    @staticmethod
+    def _place_check(rc, what):
+        # a code that is not 0 / 1 / 3 is the caller's data: ValueError with
+        # the entry point's own words, which name the cell and the mutation
+        if rc == 2:
+            msg = load().bnpc_last_error().decode('utf-8', 'replace')
+            if 'is not 0, 1 or 3' in msg:
+                raise ValueError(msg)
+        check(rc, what)
+
+    def place(self, new_data, labels, params, FN, FP, alpha,
+            prior=(.25, .25), chunk=0, slab=0, matrix=False):
+        """Where Q cells that were not part of the run belong: the Gibbs
+        conditional of one cell in every posterior sample, averaged
+        (bnpc_post_place) -> (prob_sum (Q, K), new_sum, ent_sum, lpd (Q,), lp,
+        scores), float64, as postproc.host_place defines them; with
+        matrix=True, else None, lp (S, Q) and the raw scores (S, Q, W + 1),
+        NaN where a sample has no such row.  new_data: new cells x mutations,
+        0 / 1 / missing (NaN or 3), or its uint8 codes; labels: the N labels
+        of a clustering of the training cells, compact in [0, K); params: the
+        samples x W x M trace; FN, FP, alpha: the S error rates and
+        concentrations of the samples; prior: the Beta (p, q) of the
+        parameters.  chunk: samples on the device at a time (0: about 512
+        MB); slab: new cells whose scores are resident at a time (0: what the
+        free device memory takes).  The same bits for any chunk and slab.  A
+        code other than 0 / 1 / 3 raises ValueError naming the new cell and
+        the mutation."""
+        codes, labels, K, par, (FN, FP, alpha), mix1, mix0 = self._place_args(
+            new_data, labels, params, FN, FP, alpha, prior)
+        Q, M = codes.shape
+        W = par.shape[1]
+        prob = np.empty((Q, K))
+        vec = [np.empty(Q) for _ in range(3)]
+        lp = np.empty((self.S, Q)) if matrix else None
+        scores = np.empty((self.S, Q, W + 1)) if matrix else None
+        self._place_check(load().bnpc_post_place(self._h, ptr(codes), Q, M,
+            ptr(labels), K, ptr(par), W, ptr(FN), ptr(FP), ptr(alpha), mix1,
+            mix0, int(chunk), int(slab), ptr(prob), *[ptr(x) for x in vec],
+            *[None if x is None else ptr(x) for x in (lp, scores)]),
+            'post_place')
+        return (prob,) + tuple(vec) + (lp, scores)
+
+    def place_times(self, new_data, labels, params, FN, FP, alpha,
+            prior=(.25, .25), chunk=0, slab=0):
+        """Seconds by device events, summed over one place call that brings
+        nothing back: (uploads and mask kernel, rank kernel, table kernel,
+        counts kernel, sums kernel, per-cell reductions)."""
+        codes, labels, K, par, (FN, FP, alpha), mix1, mix0 = self._place_args(
+            new_data, labels, params, FN, FP, alpha, prior)
+        ms = (C.c_float * 6)()
+        self._place_check(load().bnpc_post_place_times(self._h, ptr(codes),
+            codes.shape[0], codes.shape[1], ptr(labels), K, ptr(par),
+            par.shape[1], ptr(FN), ptr(FP), ptr(alpha), mix1, mix0,
+            int(chunk), int(slab), ms), 'post_place_times')
         return tuple(x / 1e3 for x in ms)
 
     def chain_agreement(self, bounds):

@@ -1984,3 +1984,545 @@ extern "C" int bnpc_post_doublets_times(bnpc_post *p, const uint8_t *codes,
     return db_run(p, codes, M, labels, K, theta, FN, FP, logw, lN, lT, chunk,
                   slab, out, ms);
 }
+
+// ---------------------------------------------------------------------------
+// Placement of held-out cells: the Gibbs conditional of one cell that
+// was not part of the run (libs/CRP.py:223-234 with the weights of :84-85 and
+// the mixing constants of :42-44), evaluated in every posterior sample and
+// averaged.  Per sample s, with D_s its clusters, the candidates of a new cell
+// are the sample's rows r < D_s in rank order and then a new cluster.  A row's
+// tables are those of k_cf_tables from the float32 trace and the sample's own
+// FN[s], FP[s]; the new cluster's are the constants
+//   L1 = log(mix1 * (1 - FN[s]) + mix0 * FP[s])
+//   L0 = log(mix1 * FN[s] + mix0 * (1 - FP[s]))
+// score[s][j][c] is the sum over the mutations, strictly in increasing m from
+// 0.0, of L1 where new cell j shows a 1 and L0 where it shows a 0;
+// y_c = score_c + log(n_c) for a row of n_c training cells and
+// score + log(alpha[s]) for the new cluster; mx = max y_c, e_c = exp(y_c - mx),
+// es their sum in candidate order, pr_c = e_c / es.  Per cell, one sample at a
+// time in increasing s from 0.0:
+//   prob_sum[j][k] += sum over r, in increasing r from 0.0, of
+//                     pr_r * (cnt[r][k] / n_r)
+//   new_sum[j] += pr_new     ent_sum[j] += log(es) - (sum of e_c (y_c - mx)) / es
+//   lp[s][j] = (mx + log(es)) - log(N + alpha[s])
+// with cnt[r][k] the training cells of row r that the clustering `labels` puts
+// into k, and lpd[j] = mxs + log(sum of exp(lp[s][j] - mxs)) - log(S) over the
+// column.  postproc.host_place is the host loop this is pinned to.
+//
+// Once per call the new cells go up and k_mf_masks turns them into lane masks,
+// as for -pd.  Per slab of new cells and chunk of samples:
+// k_cg_rank    all N training cells' ranks in the chunk's samples
+// k_pn_tables  thread = (candidate of the chunk, mutation): the candidates of
+//              all the chunk's samples are one flat list - each sample's D_s
+//              rows, then its new cluster - cut into tiles of DB_TILE whatever
+//              sample they belong to, in the layout k_db_sums reads
+// k_pn_counts  workgroup = sample: cnt[r][k] by integer atomics (any order, the
+//              same integers), then per row n_r, log(n_r) and the shares
+//              cnt[r][k] / n_r, each divided once; log(alpha[s]) for the new
+//              cluster and log(N + alpha[s])
+// k_db_sums    as it stands: SCO[candidate of the chunk][cell of the slab],
+//              each score bit for bit the sequential sum of the tables
+// k_pn_soft    thread = (new cell, sample): the sample's candidates in order
+//              - mx, e_c, es, pr_c (the scores' slots are reused for e_c and
+//              pr_c), the sample's entropy term and lp, which stays resident
+//              (S x slab)
+// k_pn_accum   thread = (new cell, accumulator): prob_sum[k], new_sum or
+//              ent_sum of the cell, the chunk's samples in increasing s; the
+//              accumulators stay on the device between chunks.  (One thread
+//              per new cell for all of it left a 5000-cell slab on 79 waves
+//              and took five times the sums kernel's time.)
+// and after the last chunk
+// k_pn_lpd     thread = new cell: its column of lp, the maximum first.
+// ---------------------------------------------------------------------------
+// cand[c] = (sample of the chunk, row), (sample, -1) its new cluster, (-1, -1)
+// a padding slot of the last tile; P the chunk's [.][W][M] trace, FN / FP the
+// chunk's rates
+__global__ __launch_bounds__(256) void k_pn_tables(
+    const float *__restrict__ P, int W, long long M,
+    const int2 *__restrict__ cand, int slots, const double *__restrict__ FN,
+    const double *__restrict__ FP, double mix1, double mix0,
+    double *__restrict__ T)
+{
+    const long long m = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (m >= M) return;
+    for (int c = blockIdx.y; c < slots; c += gridDim.y) {
+        const int2 qr = cand[c];
+        double l1 = 0.0, l0 = 0.0;
+        if (qr.x >= 0) {
+            const double fn = FN[qr.x], fp = FP[qr.x];
+            double t = mix1, o = mix0;
+            if (qr.y >= 0) {
+                const float th = P[((size_t)qr.x * W + qr.y) * M + m];
+                t = (double)th;
+                o = (double)(1.0f - th);
+            }
+            l1 = log(t * (1.0 - fn) + o * fp);
+            l0 = log(t * fn + o * (1.0 - fp));
+        }
+        double *dst = T + ((size_t)(c / DB_TILE) * M + m) * (2 * DB_TILE)
+            + c % DB_TILE;
+        dst[0] = l1;
+        dst[DB_TILE] = l0;
+    }
+}
+
+// one chunk of sc samples: rank its [sc][N] rows, labels the N labels in
+// [0, K), first[q] the chunk's first candidate of sample q, distinct / alpha
+// the chunk's; cnt [candidates][K] zero on entry.  lw[c] the log-weight of
+// candidate c, share the [candidates][K] shares of the rows (a new cluster's
+// row is not written), lna[q] = log(N + alpha[q])
+__global__ __launch_bounds__(256) void k_pn_counts(
+    const unsigned short *__restrict__ rank, long long N, int sc,
+    const int *__restrict__ labels, int K, const int *__restrict__ first,
+    const int *__restrict__ distinct, const double *__restrict__ alpha,
+    int *cnt, double *__restrict__ share, double *__restrict__ lw,
+    double *__restrict__ lna)
+{
+    const int tid = threadIdx.x;
+    for (int q = blockIdx.x; q < sc; q += gridDim.x) {
+        const int base = first[q], D = distinct[q];
+        const unsigned short *rk = rank + (size_t)q * N;
+        for (long long i = tid; i < N; i += 256)
+            atomicAdd(&cnt[(size_t)(base + rk[i]) * K + labels[i]], 1);
+        __threadfence();
+        __syncthreads();
+        for (int r = tid; r < D; r += 256) {
+            int *row = cnt + (size_t)(base + r) * K;
+            long long n = 0;
+            for (int k = 0; k < K; k++)
+                n += __hip_atomic_load(row + k, __ATOMIC_RELAXED,
+                                       __HIP_MEMORY_SCOPE_AGENT);
+            const double dn = (double)n;
+            lw[base + r] = log(dn);
+            double *out = share + (size_t)(base + r) * K;
+            for (int k = 0; k < K; k++)
+                out[k] = (double)__hip_atomic_load(row + k, __ATOMIC_RELAXED,
+                                                   __HIP_MEMORY_SCOPE_AGENT)
+                    / dn;
+        }
+        if (tid == 0) {
+            lw[base + D] = log(alpha[q]);
+            lna[q] = log((double)N + alpha[q]);
+        }
+    }
+}
+
+// thread = (new cell i of the slab, sample q of the chunk): the sample's
+// candidates in order down the cell's column SCO[.][off + i].  The scores'
+// slots are reused: e_c, then pr_c, which k_pn_accum reads.  ET [sc][pp] takes
+// the sample's entropy term, LP [S][pp] its log predictive density
+__global__ __launch_bounds__(256) void k_pn_soft(
+    double *__restrict__ SCO, long long pitch, long long off, long long nc,
+    int sc, long long s0, const int *__restrict__ first,
+    const int *__restrict__ distinct, const double *__restrict__ lw,
+    const double *__restrict__ lna, long long pp, double *__restrict__ ET,
+    double *__restrict__ LP)
+{
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= nc) return;
+    for (int q = blockIdx.y; q < sc; q += gridDim.y) {
+        const int base = first[q], D = distinct[q];
+        double *col = SCO + (size_t)base * pitch + off + i;
+        const double *w = lw + base;
+        double mx = col[0] + w[0];
+        for (int c = 1; c <= D; c++) {
+            const double y = col[(size_t)c * pitch] + w[c];
+            mx = y > mx ? y : mx;
+        }
+        double es = 0.0, h = 0.0;
+        for (int c = 0; c <= D; c++) {
+            const double d = (col[(size_t)c * pitch] + w[c]) - mx;
+            const double e = exp(d);
+            es += e;
+            h += e * d;
+            col[(size_t)c * pitch] = e;
+        }
+        for (int c = 0; c <= D; c++)
+            col[(size_t)c * pitch] = col[(size_t)c * pitch] / es;
+        const double les = log(es);
+        ET[(size_t)q * pp + i] = les - h / es;
+        LP[(size_t)(s0 + q) * pp + i] = (mx + les) - lna[q];
+    }
+}
+
+// thread = (new cell i of the slab, accumulator j): j < K the cell's
+// prob_sum[j], j = K its new_sum, j = K + 1 its ent_sum, each one sample at a
+// time in increasing q from where the last chunk left it.  SCO holds pr_c
+// (k_pn_soft); acc is [K + 2][pp]
+__global__ __launch_bounds__(256) void k_pn_accum(
+    const double *__restrict__ SCO, long long pitch, long long off,
+    long long nc, int sc, const int *__restrict__ first,
+    const int *__restrict__ distinct, const double *__restrict__ share, int K,
+    const double *__restrict__ ET, long long pp, double *__restrict__ acc)
+{
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= nc) return;
+    const int j = (int)blockIdx.y;
+    double sum = acc[(size_t)j * pp + i];
+    if (j == K + 1) {
+        for (int q = 0; q < sc; q++) sum += ET[(size_t)q * pp + i];
+    } else if (j == K) {
+        for (int q = 0; q < sc; q++)
+            sum += SCO[(size_t)(first[q] + distinct[q]) * pitch + off + i];
+    } else {
+        for (int q = 0; q < sc; q++) {
+            const int base = first[q], D = distinct[q];
+            const double *col = SCO + (size_t)base * pitch + off + i;
+            const double *sh = share + (size_t)base * K + j;
+            // (a share of zero adds nothing: the same bits with or without
+            // it; the share is the same in every lane)
+            double t = 0.0;
+            for (int r = 0; r < D; r++) {
+                const double f = sh[(size_t)r * K];
+                if (f != 0.0) t += col[(size_t)r * pitch] * f;
+            }
+            sum += t;
+        }
+    }
+    acc[(size_t)j * pp + i] = sum;
+}
+
+// new cell i of the slab: its column LP[0 .. S)[i] in increasing s
+__global__ __launch_bounds__(256) void k_pn_lpd(
+    const double *__restrict__ LP, long long S, long long pp, long long nc,
+    double *__restrict__ lpd)
+{
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= nc) return;
+    const double *col = LP + i;
+    double mx = col[0];
+    for (long long s = 1; s < S; s++) {
+        const double v = col[(size_t)s * pp];
+        mx = v > mx ? v : mx;
+    }
+    double es = 0.0;
+    for (long long s = 0; s < S; s++) es += exp(col[(size_t)s * pp] - mx);
+    lpd[i] = (mx + log(es)) - log((double)S);
+}
+
+namespace {
+struct PnOut {
+    double *prob_sum, *new_sum, *ent_sum, *lpd, *lp, *scores;
+};
+}  // namespace
+
+// ms (NULL, or 6 floats): device-event milliseconds summed over the call -
+// ms[0] the uploads and k_mf_masks, ms[1] k_cg_rank, ms[2] k_pn_tables, ms[3]
+// k_pn_counts (with its table's zeroing), ms[4] k_db_sums, ms[5] k_pn_soft,
+// k_pn_accum and k_pn_lpd
+static int pn_run(bnpc_post *p, const uint8_t *codes, int64_t Q, int64_t M,
+                  const int32_t *labels, int64_t K, const float *params,
+                  int64_t W, const double *FN, const double *FP,
+                  const double *alpha, double mix1, double mix0, int64_t chunk,
+                  int64_t slab, const PnOut &out, float *ms)
+{
+    if (!p || !codes || !labels || !params || !FN || !FP || !alpha || Q < 1
+        || M < 1 || (M + 255) / 256 > (int64_t)INT_MAX || K < 1
+        || K >= (int64_t)GT_MIXED || W < 1 || W >= (int64_t)GT_MIXED || chunk < 0
+        || slab < 0 || !(mix1 > 0.0 && mix1 < 1.0 && mix0 > 0.0 && mix0 < 1.0)) {
+        bnpc_set_error("bad argument: the placement needs the new cells' "
+                       "codes, Q >= 1, M >= 1, N labels, 1 <= K < 65534, a 1 <= W < "
+                       "65534 x M trace, FN, FP, alpha, mix1 and mix0 inside "
+                       "(0, 1), chunk >= 0 and slab >= 0");
+        return 2;
+    }
+    const char *const pass = "placement";
+    if (int rc = post_check_handle(pass, p)) return rc;
+    const int64_t S = p->S, N = p->N;
+    for (int64_t i = 0; i < N; i++) {
+        if (labels[i] < 0 || labels[i] >= K) {
+            bnpc_set_error("placement: label %d of cell %lld is not in [0, K = "
+                           "%lld)", (int)labels[i], (long long)i, (long long)K);
+            return 2;
+        }
+    }
+    if (int rc = post_check_rates(pass, FN, FP, S)) return rc;
+    for (int64_t s = 0; s < S; s++) {
+        if (!(std::isfinite(alpha[s]) && alpha[s] > 0.0)) {
+            bnpc_set_error("placement: alpha = %g of sample %lld is not a "
+                           "finite value above 0", alpha[s], (long long)s);
+            return 2;
+        }
+    }
+    PCK(hipSetDevice(p->device));
+    PostBuffers buf;
+    PostLaps laps;
+    PostArea area;
+    int *d_distinct;
+    if (int rc = post_check_distinct(pass, p, W, buf, area, &d_distinct))
+        return rc;
+    std::vector<int> distinct((size_t)S);
+    PCK(hipMemcpy(distinct.data(), d_distinct, S * sizeof(int),
+                  hipMemcpyDeviceToHost));
+
+    // the new cells' lane masks: every code is looked at before anything is
+    // added up
+    const int64_t nb = (Q + 63) / 64;
+    const int64_t Mp = (M + 63) / 64 * 64;
+    ulonglong2 *d_masks;
+    uint8_t *d_codes;
+    unsigned long long *d_bad;
+    POST_ALLOC(buf, pass, &d_masks, (size_t)nb * Mp);
+    POST_ALLOC(buf, pass, &d_codes, (size_t)post_mask_slab_cells(Q, M) * M);
+    POST_ALLOC(buf, pass, &d_bad, 1);
+    PCK(laps.start(ms, 6));
+    if (int rc = post_build_masks(pass, codes, nullptr, Q, M, Mp, d_codes,
+                                  d_masks, d_bad, laps, 0))
+        return rc;
+
+    // the chunk of samples: its trace and, at W + 1 candidates a sample, its
+    // tables (a launch's first dimension times its 256 threads stays below
+    // 2^32: at most 2^24 candidates), then its true candidates, the most of
+    // any chunk
+    const size_t sample_floats = (size_t)W * M;
+    int64_t sc = post_default_chunk(chunk, sample_floats * sizeof(float)
+                                    + (size_t)(W + 1) * M * 16, S);
+    sc = std::min<int64_t>(sc, std::max<int64_t>(1, ((int64_t)1 << 24)
+                                                  / (W + 1)));
+    int64_t cand_max = 0;
+    for (int64_t s0 = 0; s0 < S; s0 += sc) {
+        int64_t c = 0;
+        for (int64_t s = s0; s < std::min(S, s0 + sc); s++)
+            c += distinct[s] + 1;
+        cand_max = std::max(cand_max, c);
+    }
+    const int64_t tiles_max = (cand_max + DB_TILE - 1) / DB_TILE;
+    const int64_t slots_max = tiles_max * DB_TILE;
+    float *d_P;
+    double *d_T, *d_FN, *d_FP, *d_alpha, *d_share, *d_lw, *d_lna;
+    int2 *d_cand;
+    int *d_first, *d_labels, *d_cnt;
+    unsigned short *d_rank;
+    POST_ALLOC(buf, pass, &d_P, (size_t)sc * sample_floats);
+    POST_ALLOC(buf, pass, &d_T, (size_t)tiles_max * M * (2 * DB_TILE));
+    POST_ALLOC(buf, pass, &d_FN, (size_t)S);
+    POST_ALLOC(buf, pass, &d_FP, (size_t)S);
+    POST_ALLOC(buf, pass, &d_alpha, (size_t)S);
+    POST_ALLOC(buf, pass, &d_cand, (size_t)slots_max);
+    POST_ALLOC(buf, pass, &d_first, (size_t)sc);
+    POST_ALLOC(buf, pass, &d_labels, (size_t)N);
+    POST_ALLOC(buf, pass, &d_rank, (size_t)sc * N);
+    POST_ALLOC(buf, pass, &d_cnt, (size_t)cand_max * K);
+    POST_ALLOC(buf, pass, &d_share, (size_t)cand_max * K);
+    POST_ALLOC(buf, pass, &d_lw, (size_t)cand_max);
+    POST_ALLOC(buf, pass, &d_lna, (size_t)sc);
+    size_t free_b = 0, total_b = 0;
+    PCK(hipMemGetInfo(&free_b, &total_b));
+    // per resident new cell: its scores of a chunk, its column of lp, a
+    // chunk's entropy terms, its K + 2 sums and its lpd (the pitch of nc
+    // cells is below nc + 128)
+    const size_t per_cell = (size_t)cand_max * 8 + (size_t)S * 8
+        + (size_t)sc * 8 + (size_t)K * 8 + 24;
+    const size_t margin = (size_t)64 << 20;
+    const int64_t fit = (free_b > margin
+        ? (int64_t)std::min<size_t>((free_b - margin) / per_cell,
+                                    (size_t)1 << 40) : 0) - 128;
+    int64_t nc;
+    if (slab) {
+        nc = std::min(slab, Q);
+        if (nc > fit) nc = 0;
+    } else {
+        nc = std::min(Q, fit);
+        if (nc < Q) nc = nc / 64 * 64;          // whole blocks
+    }
+    if (nc < 1) {
+        bnpc_set_error("placement: %lld candidates and %lld samples x 64 new "
+                       "cells need %.1f GB, %.1f GB of device memory are free",
+                       (long long)cand_max, (long long)S,
+                       (margin + 192.0 * per_cell) / 1e9, free_b / 1e9);
+        return 5;
+    }
+    // (an unaligned slab of nc cells touches (nc + 62) / 64 + 1 blocks)
+    const int64_t nblk_max = nc >= Q ? nb : (nc + 62) / 64 + 1;
+    const int64_t pitch = nblk_max * 64;
+    // d_acc: [K + 2][nc] - prob_sum by cluster, new_sum, ent_sum - then lpd
+    double *d_SC, *d_acc, *d_ET, *d_LP;
+    POST_ALLOC(buf, pass, &d_SC, (size_t)cand_max * pitch);
+    POST_ALLOC(buf, pass, &d_acc, (size_t)(K + 3) * nc);
+    POST_ALLOC(buf, pass, &d_ET, (size_t)sc * nc);
+    POST_ALLOC(buf, pass, &d_LP, (size_t)S * nc);
+    double *const d_lpd = d_acc + (size_t)(K + 2) * nc;
+    laps.begin();
+    PCK(hipMemcpy(d_FN, FN, S * sizeof(double), hipMemcpyHostToDevice));
+    PCK(hipMemcpy(d_FP, FP, S * sizeof(double), hipMemcpyHostToDevice));
+    PCK(hipMemcpy(d_alpha, alpha, S * sizeof(double), hipMemcpyHostToDevice));
+    PCK(hipMemcpy(d_labels, labels, (size_t)N * sizeof(int),
+                  hipMemcpyHostToDevice));
+    laps.end(0);
+    if (out.scores) {
+        const size_t count = (size_t)S * Q * (W + 1);
+        for (size_t at = 0; at < count; at++) out.scores[at] = NAN;
+    }
+
+    std::vector<int2> cand((size_t)slots_max);
+    std::vector<int> first((size_t)sc);
+    std::vector<double> stage;
+    const bool one_chunk = sc >= S;
+    for (int64_t i0 = 0; i0 < Q; i0 += nc) {
+        const int64_t cells = std::min(nc, Q - i0);
+        const int64_t b0 = i0 / 64, off = i0 - b0 * 64;
+        const int64_t nblk = (i0 + cells - 1) / 64 - b0 + 1;
+        PCK(hipMemset(d_acc, 0, (size_t)(K + 2) * nc * sizeof(double)));
+        for (int64_t s0 = 0; s0 < S; s0 += sc) {
+            const int64_t n = std::min(sc, S - s0);
+            // the chunk's flat list of candidates
+            int64_t cn = 0;
+            for (int64_t q = 0; q < n; q++) {
+                first[q] = (int)cn;
+                for (int r = 0; r < distinct[s0 + q]; r++)
+                    cand[cn++] = make_int2((int)q, r);
+                cand[cn++] = make_int2((int)q, -1);
+            }
+            const int64_t tiles = (cn + DB_TILE - 1) / DB_TILE;
+            for (int64_t c = cn; c < tiles * DB_TILE; c++)
+                cand[c] = make_int2(-1, -1);
+            if (!one_chunk || i0 == 0) {
+                laps.begin();
+                PCK(hipMemcpy(d_P, params + (size_t)s0 * sample_floats,
+                              (size_t)n * sample_floats * sizeof(float),
+                              hipMemcpyHostToDevice));
+                PCK(hipMemcpy(d_cand, cand.data(),
+                              (size_t)tiles * DB_TILE * sizeof(int2),
+                              hipMemcpyHostToDevice));
+                PCK(hipMemcpy(d_first, first.data(), (size_t)n * sizeof(int),
+                              hipMemcpyHostToDevice));
+                laps.end(0);
+                laps.begin();
+                post_launch_rank(p, area, s0, n, 0, N, N, d_rank);
+                PCK(hipGetLastError());
+                laps.end(1);
+                laps.begin();
+                hipLaunchKernelGGL(k_pn_tables,
+                                   dim3((unsigned)((M + 255) / 256),
+                                        (unsigned)std::min<int64_t>(
+                                            tiles * DB_TILE, 65535)),
+                                   dim3(256), 0, 0, d_P, (int)W, (long long)M,
+                                   d_cand, (int)(tiles * DB_TILE), d_FN + s0,
+                                   d_FP + s0, mix1, mix0, d_T);
+                PCK(hipGetLastError());
+                laps.end(2);
+                laps.begin();
+                PCK(hipMemset(d_cnt, 0, (size_t)cn * K * sizeof(int)));
+                hipLaunchKernelGGL(k_pn_counts,
+                                   dim3((unsigned)std::min<int64_t>(n, 65535)),
+                                   dim3(256), 0, 0, d_rank, (long long)N,
+                                   (int)n, d_labels, (int)K, d_first,
+                                   d_distinct + s0, d_alpha + s0, d_cnt,
+                                   d_share, d_lw, d_lna);
+                PCK(hipGetLastError());
+                laps.end(3);
+            }
+            laps.begin();
+            hipLaunchKernelGGL(k_db_sums,
+                               dim3((unsigned)tiles,
+                                    (unsigned)std::min<int64_t>((nblk + 3) / 4,
+                                                                65535)),
+                               dim3(256), 0, 0, d_T, (int)cn, (long long)M,
+                               (long long)Mp, d_masks, (long long)b0,
+                               (long long)nblk, (long long)pitch, 0LL, d_SC);
+            PCK(hipGetLastError());
+            laps.end(4);
+            if (out.scores) {
+                // SCO is [candidate][cell]: through the host, turned
+                stage.resize((size_t)cn * cells);
+                PCK(hipMemcpy2D(stage.data(), (size_t)cells * sizeof(double),
+                                d_SC + off, (size_t)pitch * sizeof(double),
+                                (size_t)cells * sizeof(double), (size_t)cn,
+                                hipMemcpyDeviceToHost));
+                for (int64_t q = 0; q < n; q++) {
+                    const int D = distinct[s0 + q];
+                    for (int r = 0; r <= D; r++) {
+                        const double *src = stage.data()
+                            + (size_t)(first[q] + r) * cells;
+                        const int64_t slot = r < D ? r : W;
+                        for (int64_t i = 0; i < cells; i++)
+                            out.scores[((size_t)(s0 + q) * Q + i0 + i)
+                                       * (W + 1) + slot] = src[i];
+                    }
+                }
+            }
+            laps.begin();
+            hipLaunchKernelGGL(k_pn_soft,
+                               dim3((unsigned)((cells + 255) / 256),
+                                    (unsigned)std::min<int64_t>(n, 65535)),
+                               dim3(256), 0, 0, d_SC, (long long)pitch,
+                               (long long)off, (long long)cells, (int)n,
+                               (long long)s0, d_first, d_distinct + s0, d_lw,
+                               d_lna, (long long)nc, d_ET, d_LP);
+            PCK(hipGetLastError());
+            hipLaunchKernelGGL(k_pn_accum,
+                               dim3((unsigned)((cells + 255) / 256),
+                                    (unsigned)(K + 2)),
+                               dim3(256), 0, 0, d_SC, (long long)pitch,
+                               (long long)off, (long long)cells, (int)n,
+                               d_first, d_distinct + s0, d_share, (int)K, d_ET,
+                               (long long)nc, d_acc);
+            PCK(hipGetLastError());
+            laps.end(5);
+        }
+        laps.begin();
+        hipLaunchKernelGGL(k_pn_lpd, dim3((unsigned)((cells + 255) / 256)),
+                           dim3(256), 0, 0, d_LP, (long long)S, (long long)nc,
+                           (long long)cells, d_lpd);
+        PCK(hipGetLastError());
+        laps.end(5);
+        double *host[3] = {out.new_sum, out.ent_sum, out.lpd};
+        for (int k = 0; k < 3; k++)
+            if (host[k])
+                PCK(hipMemcpy(host[k] + i0, d_acc + (size_t)(K + k) * nc,
+                              cells * sizeof(double), hipMemcpyDeviceToHost));
+        if (out.lp)
+            PCK(hipMemcpy2D(out.lp + i0, (size_t)Q * sizeof(double), d_LP,
+                            (size_t)nc * sizeof(double),
+                            (size_t)cells * sizeof(double), (size_t)S,
+                            hipMemcpyDeviceToHost));
+        if (out.prob_sum) {
+            // prob is [cluster][cell]: through the host, turned
+            stage.resize((size_t)K * cells);
+            PCK(hipMemcpy2D(stage.data(), (size_t)cells * sizeof(double),
+                            d_acc, (size_t)nc * sizeof(double),
+                            (size_t)cells * sizeof(double), (size_t)K,
+                            hipMemcpyDeviceToHost));
+            for (int64_t k = 0; k < K; k++)
+                for (int64_t i = 0; i < cells; i++)
+                    out.prob_sum[(size_t)(i0 + i) * K + k]
+                        = stage[(size_t)k * cells + i];
+        }
+    }
+    PCK(hipDeviceSynchronize());
+    return laps.result(pass);
+}
+
+extern "C" int bnpc_post_place(bnpc_post *p, const uint8_t *codes, int64_t Q,
+                               int64_t M, const int32_t *labels, int64_t K,
+                               const float *params, int64_t W,
+                               const double *FN, const double *FP,
+                               const double *alpha, double mix1, double mix0,
+                               int64_t chunk, int64_t slab, double *prob_sum,
+                               double *new_sum, double *ent_sum, double *lpd,
+                               double *lp, double *scores)
+{
+    const PnOut out = {prob_sum, new_sum, ent_sum, lpd, lp, scores};
+    return pn_run(p, codes, Q, M, labels, K, params, W, FN, FP, alpha, mix1,
+                  mix0, chunk, slab, out, nullptr);
+}
+
+// diagnostic (tools/posterior_bench.py): one bnpc_post_place call without its
+// results' way back, by device events (see pn_run)
+extern "C" int bnpc_post_place_times(bnpc_post *p, const uint8_t *codes,
+                                     int64_t Q, int64_t M,
+                                     const int32_t *labels, int64_t K,
+                                     const float *params, int64_t W,
+                                     const double *FN, const double *FP,
+                                     const double *alpha, double mix1,
+                                     double mix0, int64_t chunk, int64_t slab,
+                                     float *ms)
+{
+    if (!ms) {
+        bnpc_set_error("bad argument: NULL");
+        return 2;
+    }
+    const PnOut out = {};
+    return pn_run(p, codes, Q, M, labels, K, params, W, FN, FP, alpha, mix1,
+                  mix0, chunk, slab, out, ms);
+}

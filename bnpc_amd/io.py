@@ -462,6 +462,59 @@ def save_doublets(out_dir, chain, est, tables, names=None):
     return paths
 
 
+def save_placement(out_dir, chain, est, tables, assignment, names=None):
+    """The placement files of postproc.place_cells for one (chain, estimator) row.
+    placement_<est>_<chain>.tsv: per new cell its name (`names`, the names of
+    the file of new cells, when there is one per cell, else 0..Q-1),
+    `cluster` (`new` where the cell opens a cluster of its own), `prob`,
+    `next_cluster`, `next_prob`, `p_new`, `entropy`, `n_obs`, `lpd`,
+    `lpd_per_obs`, then the probability of every cluster; cluster ids are the
+    labels of `assignment` (cluster k of the tables is the k-th smallest),
+    floats %.4f.  placement_summary_<est>_<chain>.txt: `key: value` lines -
+    samples, cells, clusters, placed (per cluster id:count), new, lpd,
+    mean_lpd_per_obs and worst_cells, the ten cells with the smallest lpd per
+    observed entry as name:value pairs."""
+    ids = np.unique(np.asarray(assignment))
+    prob = tables['prob']
+    Q, K = prob.shape
+    index = np.arange(Q)
+    if names is not None and np.asarray(names).size == Q:
+        index = np.asarray(names)
+    index = index.tolist()
+    tag = f'{chain:0>2}'
+    paths = [os.path.join(out_dir, f'placement_{est}_{tag}.tsv'),
+        os.path.join(out_dir, f'placement_summary_{est}_{tag}.txt')]
+
+    def cluster_id(k):
+        return 'new' if k < 0 else str(ids[k])
+    nxt = tables['next_cluster']
+    with open(paths[0], 'w') as f:
+        f.write('cell\tcluster\tprob\tnext_cluster\tnext_prob\tp_new\t'
+            'entropy\tn_obs\tlpd\tlpd_per_obs\t'
+            + '\t'.join(str(i) for i in ids.tolist()) + '\n')
+        for i, name in enumerate(index):
+            other = ids[nxt[i]] if nxt[i] >= 0 else -1
+            f.write(f'{name}\t{cluster_id(tables["cluster"][i])}\t'
+                f'{tables["cluster_prob"][i]:.4f}\t{other}\t'
+                f'{tables["next_prob"][i]:.4f}\t{tables["p_new"][i]:.4f}\t'
+                f'{tables["entropy"][i]:.4f}\t{int(tables["n_obs"][i])}\t'
+                f'{tables["lpd"][i]:.4f}\t{tables["lpd_per_obs"][i]:.4f}\t'
+                + '\t'.join(f'{x:.4f}' for x in prob[i].tolist()) + '\n')
+    total = tables['total']
+    per_obs = tables['lpd_per_obs']
+    with open(paths[1], 'w') as f:
+        for key in ('samples', 'cells', 'clusters'):
+            f.write(f'{key}: {total[key]}\n')
+        f.write('placed: ' + ' '.join(f'{ids[k]}:{n}'
+            for k, n in enumerate(total['placed'])) + '\n')
+        f.write(f'new: {total["new"]}\n')
+        f.write(f'lpd: {total["lpd"]:.4f}\n')
+        f.write(f'mean_lpd_per_obs: {total["mean_lpd_per_obs"]:.4f}\n')
+        f.write('worst_cells: ' + ' '.join(f'{index[i]}:{per_obs[i]:.4f}'
+            for i in total['worst_cells']) + '\n')
+    return paths
+
+
 def save_chain_agreement(out_dir, chain, est, tables, names=None):
     """The -pc files of postproc.chain_agreement for one (chain, estimator)
     row.  chain_agreement_<est>_<chain>.tsv: per cell its name (`names`, the

@@ -1032,6 +1032,222 @@ _doublet_tables = doublets      # (posterior_estimate's keyword has the name)
 
 
 # ---------------------------------------------------------------------------
+# placement of held-out cells: the Gibbs conditional of one cell that was
+# not part of the run (libs/CRP.py:223-234 with the weights of :84-85 and the
+# mixing constants of :42-44), in every posterior sample, averaged; not a
+# reference output, so the arithmetic and the summation order below are the
+# specification
+# ---------------------------------------------------------------------------
+def place_scores(new_data, assignments, params_full, FN, FP, prior):
+    """host_place's scores: (S, Q, W + 1) float64.  Per sample s, with K_s
+    its distinct labels, slot r < K_s holds the score of the new cells under
+    row r of the trace, slot W their score under a new cluster and every
+    other slot NaN.  With th = float32 params_full[s][r][m], t = float64(th),
+    o = float64(float32(1) - th) for a row and t = mix1 = p / (p + q),
+    o = mix0 = q / (p + q) for the new cluster ((p, q) = prior),
+      L1 = log(t * (1 - FN[s]) + o * FP[s])     an observed 1
+      L0 = log(t * FN[s] + o * (1 - FP[s]))     an observed 0
+    each operation rounded on its own, and a score is the sum over the
+    mutations, strictly in increasing m from 0.0, of L1 where the cell shows
+    a 1 and L0 where it shows a 0."""
+    codes = data_codes(new_data)
+    assignments = np.asarray(assignments)
+    S = assignments.shape[0]
+    Q, M = codes.shape
+    W = params_full.shape[1]
+    FN = np.asarray(FN, dtype=np.float64)
+    FP = np.asarray(FP, dtype=np.float64)
+    p, q = (float(x) for x in prior)
+    mix1, mix0 = p / (p + q), q / (p + q)
+    is1, is0 = codes == 1, codes == 0
+    scores = np.full((S, Q, W + 1), np.nan)
+    for s in range(S):
+        Ks = np.unique(assignments[s]).size
+        th = np.asarray(params_full[s], dtype=np.float32)[:Ks]
+        t = np.append(th.astype(np.float64), np.full((1, M), mix1), axis=0)
+        o = np.append((np.float32(1) - th).astype(np.float64),
+            np.full((1, M), mix0), axis=0)
+        L1 = np.log(t * (1 - FN[s]) + o * FP[s])
+        L0 = np.log(t * FN[s] + o * (1 - FP[s]))
+        sc = np.zeros((Q, Ks + 1))
+        for m in range(M):
+            # (adding 0.0 leaves every bit: no partial sum is -0.0)
+            sc += np.where(is1[:, m, None], L1[:, m],
+                np.where(is0[:, m, None], L0[:, m], 0.0))
+        scores[s, :, :Ks] = sc[:, :Ks]
+        scores[s, :, W] = sc[:, Ks]
+    return scores
+
+
+def place_reduce(scores, assignments, labels, K, alpha, keep=False):
+    """host_place's reductions of an (S, Q, W + 1) array of scores (the
+    layout of place_scores): per sample the candidates in order - the rows
+    r < K_s, then the new cluster - and per cell one sample at a time in
+    increasing s.  -> {'prob_sum' (Q, K), 'new_sum', 'ent_sum', 'lpd' (Q,),
+    'lp' (S, Q)} and, with keep=True, 'y' (S, Q, W + 1): the candidates'
+    y_c in the layout of the scores."""
+    scores = np.asarray(scores, dtype=np.float64)
+    assignments = np.asarray(assignments)
+    labels = np.asarray(labels, dtype=np.int64)
+    alpha = np.asarray(alpha, dtype=np.float64)
+    S, N = assignments.shape
+    Q, W = scores.shape[1], scores.shape[2] - 1
+    prob_sum = np.zeros((Q, K))
+    new_sum, ent_sum = np.zeros(Q), np.zeros(Q)
+    lp = np.empty((S, Q))
+    ys = np.full(scores.shape, np.nan) if keep else None
+    for s in range(S):
+        rank = np.unique(assignments[s], return_inverse=True)[1].ravel()
+        Ks = int(rank.max()) + 1
+        cnt = np.zeros((Ks, K), dtype=np.int64)
+        np.add.at(cnt, (rank, labels), 1)
+        n = cnt.sum(axis=1)
+        share = cnt.astype(np.float64) / n.astype(np.float64)[:, None]
+        y = np.empty((Q, Ks + 1))
+        y[:, :Ks] = scores[s, :, :Ks] + np.log(n.astype(np.float64))
+        y[:, Ks] = scores[s, :, W] + np.log(alpha[s])
+        mx = y.max(axis=1)
+        e = np.empty_like(y)
+        es, h = np.zeros(Q), np.zeros(Q)
+        for c in range(Ks + 1):
+            d = y[:, c] - mx
+            e[:, c] = np.exp(d)
+            es += e[:, c]
+            h += e[:, c] * d
+        pr = e / es[:, None]
+        t = np.zeros((Q, K))
+        for r in range(Ks):
+            t += pr[:, r, None] * share[r]
+        prob_sum += t
+        new_sum += pr[:, Ks]
+        les = np.log(es)
+        ent_sum += les - h / es
+        lp[s] = (mx + les) - np.log(N + alpha[s])
+        if keep:
+            ys[s, :, :Ks] = y[:, :Ks]
+            ys[s, :, W] = y[:, Ks]
+    mxs = lp.max(axis=0)
+    acc = np.zeros(Q)
+    for s in range(S):
+        acc += np.exp(lp[s] - mxs)
+    out = {'prob_sum': prob_sum, 'new_sum': new_sum, 'ent_sum': ent_sum,
+        'lpd': mxs + np.log(acc) - np.log(S), 'lp': lp}
+    if keep:
+        out['y'] = ys
+    return out
+
+
+def host_place(new_data, assignments, labels, params_full, FN, FP, alpha,
+        prior, keep=True):
+    """Where cells that were not part of the run belong: the Gibbs
+    conditional of one cell in every posterior sample, averaged; the plain
+    loop bnpc_post_place is pinned to.  new_data: Q x M, 0 / 1 / missing (NaN
+    or 3); assignments: S x N, any integer labels; labels: the N labels of
+    the MPEAR clustering, compact in [0, K); params_full: S x W x M float32;
+    FN, FP, alpha: the S error rates and concentrations of the samples; prior:
+    the Beta (p, q) of the parameters.  Per sample s, r(i) is the rank of
+    training cell i's label among the sample's K_s distinct labels, n_r the
+    cells of row r and cnt[r][k] those of them with MPEAR label k; the
+    candidates c of a new cell are the rows r < K_s, then a new cluster, and
+    their scores those of place_scores.  Then
+      y_c = score_c + log(n_c), or score + log(alpha[s]) for the new cluster
+      mx = max y_c, e_c = exp(y_c - mx), es = the sum of e_c in candidate
+      order from 0.0, pr_c = e_c / es
+    and per new cell j, one sample at a time in increasing s from 0.0,
+      prob_sum[j][k] += the sum over r, in increasing r from 0.0, of
+                        pr_r * (cnt[r][k] / n_r)
+      new_sum[j]     += pr of the new cluster
+      ent_sum[j]     += log(es) - (the sum of e_c * (y_c - mx)) / es
+      lp[s][j]        = (mx + log(es)) - log(N + alpha[s])
+      lpd[j]          = mxs + log(sum over s of exp(lp[s][j] - mxs)) - log(S)
+    with mxs the column's maximum.  lp[s][j] is the log predictive density of
+    the row in sample s; an all-missing row has score 0 everywhere, the CRP
+    weights n_k / (N + alpha) as its probabilities and lp = 0.
+    -> {'prob_sum', 'new_sum', 'ent_sum', 'lpd', 'lp', 'n_obs' (Q,) int64} and,
+    with keep=True, 'scores' and 'y' (S, Q, W + 1)."""
+    codes = data_codes(new_data)
+    labels = np.asarray(labels, dtype=np.int64)
+    assignments = np.asarray(assignments)
+    if labels.shape != (assignments.shape[1],) or labels.min() < 0:
+        raise ValueError('one label >= 0 per training cell')
+    alpha = np.asarray(alpha, dtype=np.float64)
+    if not (np.isfinite(alpha) & (alpha > 0)).all():
+        raise ValueError('alpha must be finite and > 0')
+    if codes.shape[1] != params_full.shape[2]:
+        raise ValueError(f'the new cells must have the {params_full.shape[2]} '
+            f'mutations of the trace, not {codes.shape[1]}')
+    K = int(labels.max()) + 1
+    scores = place_scores(codes, assignments, params_full, FN, FP, prior)
+    out = place_reduce(scores, assignments, labels, K, alpha, keep=keep)
+    out['n_obs'] = (codes != 3).sum(axis=1).astype(np.int64)
+    if keep:
+        out['scores'] = scores
+    return out
+
+
+def place_cells(post, new_data, assignments, labels, params_full, FN, FP,
+        alpha, prior=(.25, .25)):
+    """The placement tables: where do cells that were not clustered belong?  Per
+    new cell: 'prob' (Q, K), the posterior probability that a cell drawn at
+    random from the cluster the new cell joins belongs to MPEAR cluster k,
+    and 'p_new', that it opens a cluster of its own (together they sum to
+    1); 'cluster' (the arg-max of prob, ties to the smaller index, or -1
+    where p_new exceeds every prob) and 'cluster_prob' (its probability);
+    'next_cluster' and 'next_prob' (the best MPEAR cluster other than
+    `cluster`; -1 and 0 with one cluster); 'entropy' (the mean entropy of the
+    allocation over the samples), 'n_obs', 'lpd' (the out-of-sample log
+    predictive density of the row) and 'lpd_per_obs' (0 without
+    observations).  'total': {'samples', 'cells', 'clusters', 'placed' (the
+    count per cluster), 'new', 'lpd', 'mean_lpd_per_obs' (the sum of lpd over
+    the observed entries of all new cells), 'worst_cells' (the ten with the
+    smallest lpd_per_obs, ties to the smaller index)}.  From an open
+    clustering handle: the device pass (Posterior.place) where the handle has
+    one, else the host loop (host_place); the same arithmetic on the sums
+    either way."""
+    codes = data_codes(new_data)
+    labels = np.asarray(labels, dtype=np.int64)
+    S = np.asarray(assignments).shape[0]
+    device = getattr(post, 'place', None)
+    if device is not None:
+        prob_sum, new_sum, ent_sum, lpd = device(codes, labels, params_full,
+            FN, FP, alpha, prior)[:4]
+    else:
+        red = host_place(codes, assignments, labels, params_full, FN, FP,
+            alpha, prior, keep=False)
+        prob_sum, new_sum, ent_sum, lpd = (red[k] for k in ('prob_sum',
+            'new_sum', 'ent_sum', 'lpd'))
+    n_obs = (codes != 3).sum(axis=1).astype(np.int64)
+    Q, K = prob_sum.shape
+    cells = np.arange(Q)
+    prob, p_new = prob_sum / S, new_sum / S
+    best = np.argmax(prob, axis=1).astype(np.int64)
+    cluster = np.where(p_new > prob[cells, best], -1, best)
+    cluster_prob = np.where(cluster < 0, p_new, prob[cells, best])
+    if K > 1:
+        others = prob.copy()
+        placed = cluster >= 0
+        others[cells[placed], cluster[placed]] = -np.inf
+        next_cluster = np.argmax(others, axis=1).astype(np.int64)
+        next_prob = others[cells, next_cluster]
+    else:
+        next_cluster = np.full(Q, -1, dtype=np.int64)
+        next_prob = np.zeros(Q)
+    per_obs = np.zeros(Q)
+    np.divide(lpd, n_obs, out=per_obs, where=n_obs > 0)
+    observed = int(n_obs.sum())
+    return {'prob': prob, 'p_new': p_new, 'cluster': cluster,
+        'cluster_prob': cluster_prob, 'next_cluster': next_cluster,
+        'next_prob': next_prob, 'entropy': ent_sum / S, 'n_obs': n_obs,
+        'lpd': lpd, 'lpd_per_obs': per_obs,
+        'total': {'samples': int(S), 'cells': int(Q), 'clusters': int(K),
+            'placed': np.bincount(cluster[cluster >= 0], minlength=K).tolist(),
+            'new': int((cluster < 0).sum()), 'lpd': float(lpd.sum()),
+            'mean_lpd_per_obs': float(lpd.sum()) / observed if observed
+                else 0.0,
+            'worst_cells': np.argsort(per_obs, kind='stable')[:10].tolist()}}
+
+
+# ---------------------------------------------------------------------------
 # between-chain agreement of the clustering (-pc): every chain's co-clustering
 # against that of the other chains pooled - not a reference output, so the
 # integers below are the specification

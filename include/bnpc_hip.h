@@ -1216,6 +1216,66 @@ int bnpc_post_doublets_times(bnpc_post *post, const uint8_t *codes, int64_t M,
                              const double *theta, double FN, double FP,
                              const double *logw, double lN, double lT,
                              int64_t chunk, int64_t slab, float *ms);
+/* Placement of held-out cells (not a reference output): where do Q cells
+ * that were not part of the run belong?  The Gibbs conditional of one cell
+ * (the reference's CRP.get_lpost_single and get_lpost_single_new_cluster,
+ * libs/CRP.py:223-234, with the weights of log_CRP_prior, :84-85, and the
+ * prior-predictive mixing constants of :42-44), evaluated in every sample of
+ * the post for every new cell and averaged over the samples.  codes: the new
+ * cells' Q x M codes; labels: the N labels of a clustering of the training
+ * cells, in [0, K); params: the S x W x M float32 trace, the row of a training
+ * cell in sample s the rank r of its label among the sample's D_s distinct
+ * labels (rows >= D_s are not read); FN, FP, alpha: the S error rates and
+ * concentrations of the samples; mix1 = p / (p + q), mix0 = q / (p + q) for the
+ * Beta(p, q) parameter prior.  Per sample the candidates of a new cell are the
+ * rows r < D_s, then a new cluster; with th = params[s][r][m], t = (double)th,
+ * o = (double)(1.0f - th) for a row and t = mix1, o = mix0 for the new cluster,
+ *   L1 = log(t * (1 - FN[s]) + o * FP[s]),  L0 = log(t * FN[s] + o * (1 - FP[s]))
+ * (every operation rounded on its own),
+ *   score[s][j][c]  the sum over the mutations, strictly in increasing m from
+ *                   0.0, of L1 where codes[j][m] == 1 and L0 where it is 0
+ *   y_c             score_c + log(n_c), n_c the training cells of the row, or
+ *                   score + log(alpha[s]) for the new cluster
+ *   mx = max y_c, e_c = exp(y_c - mx), es = their sum in candidate order,
+ *   pr_c = e_c / es
+ * and per new cell, one sample at a time in increasing s from 0.0,
+ *   prob_sum[j][k] += the sum over r, in increasing r from 0.0, of
+ *                     pr_r * (cnt[r][k] / n_r), cnt[r][k] the training cells
+ *                     of row r with label k
+ *   new_sum[j]     += pr of the new cluster
+ *   ent_sum[j]     += log(es) - (sum of e_c * (y_c - mx)) / es
+ *   lp[s][j]        = (mx + log(es)) - log(N + alpha[s])
+ *   lpd[j]          = mxs + log(sum over s of exp(lp[s][j] - mxs)) - log(S),
+ *                     mxs the column's maximum
+ * as bnpc_amd.postproc.host_place defines them.  scores (S x Q x (W + 1)): row
+ * r < D_s at [r], the new cluster at [W], every other slot NaN.  chunk: the
+ * samples whose trace and tables are on the device at a time (0: about 512
+ * MB); slab: the new cells whose scores are on the device at a time (0: as
+ * many as the free device memory takes).  Every output has the same bits for
+ * any chunk and slab, on every call; each may be NULL.  Return code 2 for a
+ * label outside [0, K), a rate not strictly inside (0, 1), an alpha that is
+ * not finite and > 0, mix1 or mix0 outside (0, 1), a sample with more than W
+ * clusters or a code other than 0 / 1 / 3 (named by new cell and mutation); 5
+ * if 64 new cells do not fit the device's free memory. */
+int bnpc_post_place(bnpc_post *post, const uint8_t *codes /* Q x M: 0|1|3 */,
+                    int64_t Q, int64_t M, const int32_t *labels /* N */,
+                    int64_t K, const float *params /* S x W x M */, int64_t W,
+                    const double *FN, const double *FP,
+                    const double *alpha /* S each */, double mix1, double mix0,
+                    int64_t chunk, int64_t slab,
+                    double *prob_sum /* Q x K */, double *new_sum,
+                    double *ent_sum, double *lpd /* Q each */,
+                    double *lp /* S x Q, or NULL */,
+                    double *scores /* S x Q x (W + 1), or NULL */);
+/* diagnostic: one bnpc_post_place call without its results' way back,
+ * milliseconds by device events summed over the call - ms[0] the uploads and
+ * the mask kernel, ms[1] the rank kernel, ms[2] the table kernel, ms[3] the
+ * counts kernel, ms[4] the sums kernel, ms[5] the per-cell reductions */
+int bnpc_post_place_times(bnpc_post *post, const uint8_t *codes, int64_t Q,
+                          int64_t M, const int32_t *labels, int64_t K,
+                          const float *params, int64_t W, const double *FN,
+                          const double *FP, const double *alpha, double mix1,
+                          double mix0, int64_t chunk, int64_t slab, float *ms);
 /* Between-chain agreement of the clustering (-pc; not a reference output): is
  * one chain's co-clustering that of the others?  The post's samples are the
  * chains' pooled samples, chain after chain; bounds (C + 1 int64, 0 = b_0 <

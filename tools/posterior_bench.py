@@ -56,7 +56,19 @@ events, the fastest of CHAINS_REPS (default 5) each
 (Posterior.chain_agreement_times), the label compares per second of both and
 the atomics the pass issues at most; then the call with its three tables
 brought to the host and - CHAINS_HOST=1 - the host loop
-(postproc.host_chain_agreement) compared with it; then exit."""
+(postproc.host_chain_agreement) compared with it; then exit.
+PLACE=1: right after the pair counts are made, the placement pass
+(bnpc_post_place) of PLACE_Q (default N) new cells x PLACE_M (default 1000)
+mutations of random data (30 % missing) against a random float32 trace of
+PLACE_W (default C + 8) rows per sample, PLACE_CHUNK samples and PLACE_SLAB new
+cells at a time (0: the defaults): PLACE_REPS (default 3) calls by device
+events (Posterior.place_times) - the fastest one's uploads and mask kernel,
+k_cg_rank, k_pn_tables, k_pn_counts, k_db_sums and the reductions, the scores
+per second of k_db_sums - then the call with its results brought to the host,
+then k_db_sums of the doublet pass at the same new cells and the nearest
+number of candidates, its scores per second and the ratio of the two; with
+PLACE_HOST=<samples>,<new cells> the host loop (postproc.host_place) and the
+device on that many of both; then exit."""
 import os
 import sys
 import time
@@ -185,6 +197,79 @@ if os.environ.get('DOUBLETS') == '1':
             '; max |ll_pair dev - host| =',
             float(np.abs(got[3] - want['ll_pair']).max()))
     post.close()
+    sys.exit(0)
+if os.environ.get('PLACE') == '1':
+    M = int(os.environ.get('PLACE_M', '1000'))
+    Q = int(os.environ.get('PLACE_Q', str(N)))
+    W = int(os.environ.get('PLACE_W', str(C + 8)))
+    chunk = int(os.environ.get('PLACE_CHUNK', '0'))
+    slab = int(os.environ.get('PLACE_SLAB', '0'))
+    reps = int(os.environ.get('PLACE_REPS', '3'))
+    labels = np.unique(base, return_inverse=True)[1]
+    params = np.empty((S, W, M), dtype=np.float32)
+    for s in range(S):
+        params[s] = np.clip(rng.random_sample((W, M)), 1e-3, 1 - 1e-3)
+    new = (rng.random_sample((Q, M)) < 0.3).astype(np.uint8)
+    new[rng.random_sample((Q, M)) < 0.3] = 3
+    FN, FP = rng.uniform(0.1, 0.3, S), rng.uniform(1e-4, 1e-2, S)
+    alpha = rng.uniform(0.5, 5.0, S)
+    cands = int(sum(np.unique(row).size + 1 for row in a))
+    steps = Q * cands * M
+    print(f'placement: Q={Q} M={M} W={W} chunk={chunk} slab={slab}, trace '
+        f'{params.nbytes / 1e9:.2f} GB, {cands} candidates over the samples, '
+        f'{steps:.3e} (cell, candidate, mutation) steps')
+    runs = []
+    for r in range(reps):
+        t = post.place_times(new, labels, params, FN, FP, alpha, chunk=chunk,
+            slab=slab)
+        runs.append((sum(t),) + t)
+        print(f'  rep {r}: uploads + k_mf_masks {t[0] * 1e3:.3f} ms  k_cg_rank '
+            f'{t[1] * 1e3:.3f} ms  k_pn_tables {t[2] * 1e3:.3f} ms  '
+            f'k_pn_counts {t[3] * 1e3:.3f} ms  k_db_sums {t[4] * 1e3:.3f} ms  '
+            f'k_pn_soft + k_pn_accum + k_pn_lpd {t[5] * 1e3:.3f} ms', flush=True)
+    total, _, _, _, _, p_sum, _ = min(runs)
+    print(f'  fastest of {reps} (device events): pass {total * 1e3:.3f} ms; '
+        f'k_db_sums {Q * cands / p_sum:.3e} scores/s', flush=True)
+    t0 = time.perf_counter()
+    got = post.place(new, labels, params, FN, FP, alpha, chunk=chunk,
+        slab=slab)
+    t0 = lap('Posterior.place (call, Q x K table and vectors to the host)', t0)
+    post.close()
+    # the doublet pass' k_db_sums at the same Q and M and the smallest number
+    # of candidates K (K + 1) / 2 that is not below the placement's
+    K = 1
+    while K * (K + 1) // 2 < cands:
+        K += 1
+    P = K * (K + 1) // 2
+    dlab = rng.permutation(np.arange(Q) % K).astype(np.int32)
+    theta = np.clip(rng.random_sample((K, M)), 1e-3, 1 - 1e-3)
+    other = _lib.Posterior(np.stack([dlab, dlab]))
+    runs = []
+    for r in range(reps):
+        t = other.doublets_times(new, dlab, theta, 0.2, 0.001)
+        runs.append((t[2], t))
+    d_sum = min(runs)[0]
+    other.close()
+    print(f'  doublets at Q={Q} M={M} K={K} P={P}: k_db_sums '
+        f'{d_sum * 1e3:.3f} ms, {Q * P / d_sum:.3e} scores/s; placement / '
+        f'doublets scores per second {(Q * cands / p_sum) / (Q * P / d_sum):.3f}',
+        flush=True)
+    if os.environ.get('PLACE_HOST'):
+        Sh, Qh = (int(x) for x in os.environ['PLACE_HOST'].split(','))
+        t0 = time.perf_counter()
+        want = postproc.host_place(new[:Qh], a[:Sh], labels, params[:Sh],
+            FN[:Sh], FP[:Sh], alpha[:Sh], (.25, .25), keep=False)
+        t0 = lap(f'host loop (postproc.host_place) at S={Sh} Q={Qh}', t0)
+        small = _lib.Posterior(a[:Sh])
+        t0 = time.perf_counter()
+        have = small.place(new[:Qh], labels, params[:Sh], FN[:Sh], FP[:Sh],
+            alpha[:Sh])
+        t0 = lap(f'Posterior.place at S={Sh} Q={Qh}', t0)
+        small.close()
+        print('  max |prob_sum dev - host| =',
+            float(np.abs(have[0] - want['prob_sum']).max()),
+            '; max |lpd dev - host| =',
+            float(np.abs(have[3] - want['lpd']).max()))
     sys.exit(0)
 CELLS_M = int(os.environ.get('CELLS_M', '0'))
 if CELLS_M:
