@@ -224,6 +224,27 @@ def _write_rows(path, header, tokens, cols):
         blob, _lib.ptr(off), col.size, _lib.ptr(col)), 'write_table')
 
 
+def _row_names(names, n):
+    """The names of n rows: `names` where there is one per row, else
+    0..n-1."""
+    if names is not None and np.asarray(names).size == n:
+        return np.asarray(names)
+    return np.arange(n)
+
+
+def _paths(out_dir, files, est, chain):
+    """The output paths of one (chain, estimator) row: <stem>_<est>_<chain>
+    with its extension for every <stem>.<ext> of `files`."""
+    tag = f'{chain:0>2}'
+    return [os.path.join(out_dir, f'{stem}_{est}_{tag}{ext}')
+        for stem, ext in map(os.path.splitext, files)]
+
+
+def _name_values(index, values, rows):
+    """`name:value` of the selected rows, values %.4f, space separated."""
+    return ' '.join(f'{index[i]}:{values[i]:.4f}' for i in rows)
+
+
 def save_geno(out_dir, chain, est, values, cols, header, names=None):
     """`save_geno` of the reference for one (chain, estimator) row: the
     mutations x cells genotype table whose cell c is column cols[c] of
@@ -309,20 +330,15 @@ def save_cell_geno(out_dir, chain, est, tables, names=None):
     and rows are named by them where there is one per cell / mutation, else
     0..N-1 / 0..M-1."""
     N, M = tables['mean'].shape
-    cells, muts = np.arange(N), np.arange(M)
-    if names is not None and np.asarray(names[0]).size == N:
-        cells = np.asarray(names[0])
-    if names is not None and np.asarray(names[1]).size == M:
-        muts = np.asarray(names[1])
+    cells, muts = (_row_names(None if names is None else names[k], n)
+        for k, n in enumerate((N, M)))
     index = np.array([str(x) for x in muts.tolist()], dtype=object)
-    tag = f'{chain:0>2}'
-    paths = []
-    for kind, key in (('prob', 'prob'), ('cont', 'mean'), ('sd', 'sd')):
-        path = os.path.join(out_dir, f'genotypes_cell_{kind}_{est}_{tag}.tsv')
+    paths = _paths(out_dir, ('genotypes_cell_prob.tsv',
+        'genotypes_cell_cont.tsv', 'genotypes_cell_sd.tsv'), est, chain)
+    for path, key in zip(paths, ('prob', 'mean', 'sd')):
         entries = np.char.mod('%.4f', np.asarray(tables[key]).T)
         _write_rows(path, cells.tolist(), np.concatenate([index[:, None],
             entries.astype(object)], axis=1), np.arange(N))
-        paths.append(path)
     return paths
 
 
@@ -338,14 +354,8 @@ def save_cell_fit(out_dir, chain, est, fit, assignment, names=None):
     cell) and worst_cells, the ten cells with the smallest mean
     log-likelihood per observed entry as name:value pairs."""
     assignment = np.asarray(assignment)
-    N = assignment.size
-    index = np.arange(N)
-    if names is not None and np.asarray(names).size == N:
-        index = np.asarray(names)
-    index = index.tolist()
-    tag = f'{chain:0>2}'
-    paths = [os.path.join(out_dir, f'cell_fit_{est}_{tag}.tsv'),
-        os.path.join(out_dir, f'model_fit_{est}_{tag}.txt')]
+    index = _row_names(names, assignment.size).tolist()
+    paths = _paths(out_dir, ('cell_fit.tsv', 'model_fit.txt'), est, chain)
     columns = ('mean_ll', 'sd_ll', 'lppd', 'p_waic', 'mean_ll_per_obs')
     with open(paths[0], 'w') as f:
         f.write('cell\tcluster\tn_obs\t' + '\t'.join(columns) + '\n')
@@ -361,8 +371,8 @@ def save_cell_fit(out_dir, chain, est, fit, assignment, names=None):
         for key, val in (('lppd', total['lppd']), ('p_waic', total['p_waic']),
                 ('WAIC', total['waic'])):
             f.write(f'{key}: {val:.4f}\n')
-        f.write('worst_cells: ' + ' '.join(f'{index[i]}:{per_obs[i]:.4f}'
-            for i in worst.tolist()) + '\n')
+        f.write('worst_cells: ' + _name_values(index, per_obs, worst.tolist())
+            + '\n')
     return paths
 
 
@@ -380,14 +390,9 @@ def save_mutation_fit(out_dir, chain, est, fit, names=None):
     FN_model among those with at least one expected carrier per sample), as
     name:value pairs."""
     from bnpc_amd.postproc import MUTATION_FIT_COLUMNS as columns
-    M = fit['n_obs'].size
-    index = np.arange(M)
-    if names is not None and np.asarray(names).size == M:
-        index = np.asarray(names)
-    index = index.tolist()
-    tag = f'{chain:0>2}'
-    paths = [os.path.join(out_dir, f'mutation_fit_{est}_{tag}.tsv'),
-        os.path.join(out_dir, f'mutation_summary_{est}_{tag}.txt')]
+    index = _row_names(names, fit['n_obs'].size).tolist()
+    paths = _paths(out_dir, ('mutation_fit.tsv', 'mutation_summary.txt'),
+        est, chain)
     fine = ('FP_model', 'FP_call')
 
     def cell(key, val):
@@ -410,11 +415,10 @@ def save_mutation_fit(out_dir, chain, est, fit, names=None):
             f.write(f'{key}: {total[key]}\n')
         for key in ('FN_model', 'FP_model', 'FN_call', 'FP_call', 'FN', 'FP'):
             f.write(f'{key}: {cell(key, total[key])}\n')
-        f.write('worst_mutations: ' + ' '.join(f'{index[m]}:{per_obs[m]:.4f}'
-            for m in worst.tolist()) + '\n')
-        f.write('highest_FN: ' + ' '.join(
-            f'{index[m]}:{fit["FN_model"][m]:.4f}' for m in high.tolist())
-            + '\n')
+        f.write('worst_mutations: '
+            + _name_values(index, per_obs, worst.tolist()) + '\n')
+        f.write('highest_FN: '
+            + _name_values(index, fit['FN_model'], high.tolist()) + '\n')
     return paths
 
 
@@ -430,13 +434,9 @@ def save_doublets(out_dir, chain, est, tables, names=None):
     top_cells, the ten cells with the largest p_doublet (ties: the larger
     delta, then the smaller index) as name:value pairs."""
     N = tables['p_doublet'].size
-    index = np.arange(N)
-    if names is not None and np.asarray(names).size == N:
-        index = np.asarray(names)
-    index = index.tolist()
-    tag = f'{chain:0>2}'
-    paths = [os.path.join(out_dir, f'doublets_{est}_{tag}.tsv'),
-        os.path.join(out_dir, f'doublet_summary_{est}_{tag}.txt')]
+    index = _row_names(names, N).tolist()
+    paths = _paths(out_dir, ('doublets.tsv', 'doublet_summary.txt'), est,
+        chain)
     columns = ('cluster', 'n_obs', 'll_cluster', 'best_cluster', 'll_best',
         'pair_a', 'pair_b', 'll_pair', 'delta', 'p_doublet')
     whole = ('cluster', 'n_obs', 'best_cluster', 'pair_a', 'pair_b')
@@ -457,8 +457,7 @@ def save_doublets(out_dir, chain, est, tables, names=None):
         f.write(f'called: {total["called"]}\n')
         f.write('pair_counts: ' + ' '.join(f'{a}-{b}:{n}'
             for (a, b), n in total['pair_counts'].items()) + '\n')
-        f.write('top_cells: ' + ' '.join(f'{index[i]}:{p[i]:.4f}'
-            for i in top) + '\n')
+        f.write('top_cells: ' + _name_values(index, p, top) + '\n')
     return paths
 
 
@@ -476,14 +475,9 @@ def save_placement(out_dir, chain, est, tables, assignment, names=None):
     observed entry as name:value pairs."""
     ids = np.unique(np.asarray(assignment))
     prob = tables['prob']
-    Q, K = prob.shape
-    index = np.arange(Q)
-    if names is not None and np.asarray(names).size == Q:
-        index = np.asarray(names)
-    index = index.tolist()
-    tag = f'{chain:0>2}'
-    paths = [os.path.join(out_dir, f'placement_{est}_{tag}.tsv'),
-        os.path.join(out_dir, f'placement_summary_{est}_{tag}.txt')]
+    index = _row_names(names, prob.shape[0]).tolist()
+    paths = _paths(out_dir, ('placement.tsv', 'placement_summary.txt'), est,
+        chain)
 
     def cluster_id(k):
         return 'new' if k < 0 else str(ids[k])
@@ -510,8 +504,8 @@ def save_placement(out_dir, chain, est, tables, assignment, names=None):
         f.write(f'new: {total["new"]}\n')
         f.write(f'lpd: {total["lpd"]:.4f}\n')
         f.write(f'mean_lpd_per_obs: {total["mean_lpd_per_obs"]:.4f}\n')
-        f.write('worst_cells: ' + ' '.join(f'{index[i]}:{per_obs[i]:.4f}'
-            for i in total['worst_cells']) + '\n')
+        f.write('worst_cells: '
+            + _name_values(index, per_obs, total['worst_cells']) + '\n')
     return paths
 
 
@@ -528,13 +522,9 @@ def save_chain_agreement(out_dir, chain, est, tables, names=None):
     separated by `;`) and unstable_cells, the ten cells with the largest
     worst_diff (ties: the smaller index) as name:value pairs."""
     N, C = tables['diff'].shape
-    index = np.arange(N)
-    if names is not None and np.asarray(names).size == N:
-        index = np.asarray(names)
-    index = index.tolist()
-    tag = f'{chain:0>2}'
-    paths = [os.path.join(out_dir, f'chain_agreement_{est}_{tag}.tsv'),
-        os.path.join(out_dir, f'chain_summary_{est}_{tag}.txt')]
+    index = _row_names(names, N).tolist()
+    paths = _paths(out_dir, ('chain_agreement.tsv', 'chain_summary.txt'),
+        est, chain)
     with open(paths[0], 'w') as f:
         f.write('cell\tcluster\tworst_chain\tworst_diff\t' + '\t'.join(
             f'diff_{c}\tmax_{c}\tflips_{c}' for c in range(C)) + '\n')
@@ -562,8 +552,8 @@ def save_chain_agreement(out_dir, chain, est, tables, names=None):
         f.write('cluster_diff: ' + '; '.join(f'{int(k)} ' + ' '.join(
             f'{x:.4f}' for x in row) for k, row in zip(tables['clusters'],
             tables['cluster_diff'])) + '\n')
-        f.write('unstable_cells: ' + ' '.join(f'{index[i]}:{worst[i]:.4f}'
-            for i in top.tolist()) + '\n')
+        f.write('unstable_cells: '
+            + _name_values(index, worst, top.tolist()) + '\n')
     return paths
 
 

@@ -220,3 +220,64 @@ def test_hamming_orientation_square_and_nan():
     # half-to-even: 0.5 calls 0, 1.5 calls 2
     assert postproc.hamming_similarity(np.array([[0.5, 1.5]]),
         np.array([0]), np.array([[0., 2.]])) == 1.0
+
+
+POSTERIOR_FLAGS = {'-ps': 'posterior_support', '-pg': 'posterior_genotypes',
+    '-pf': 'posterior_fit', '-pm': 'posterior_mutations',
+    '-pd': 'posterior_doublets', '-pc': 'posterior_chains'}
+FILES_PER_FLAG = {'-ps': 2, '-pg': 3, '-pf': 2, '-pm': 2, '-pd': 2, '-pc': 2}
+SUMMARY_LINES = ['posterior fit', 'posterior mutations', 'posterior doublets',
+    'posterior chains']
+
+
+def listed(out):
+    """the posterior flags of an output directory's args.txt"""
+    return [ln.split(':')[0] for ln in (out / 'args.txt').read_text()
+        .splitlines() if ln.startswith('posterior_')]
+
+
+def test_all_posterior_flags_write_what_each_writes_alone(tmp_path,
+        monkeypatch, capsys):
+    """The run with every optional table of the posterior writes what the
+    runs with one flag each write, lists the flags in args.txt and prints
+    each summary line once.  Every pass takes its host loop (FakePosterior);
+    the two chains are those of test_chain_agreement's command-line runs."""
+    import run_BnpC
+    from test_chain_agreement import ROOT, run_cli
+    golden = os.path.join(ROOT, 'tests', 'golden', 'example_data.csv')
+    _, results = run_cli(tmp_path, monkeypatch, 'chains', '-v', '0')
+    data, names = bio.load_data(golden, get_names=True)
+
+    def save(name, *flags):
+        out = tmp_path / name
+        out.mkdir()
+        args = run_BnpC.parse_args([golden, '-n', '2', '-o', str(out),
+            *flags])
+        run_BnpC.save_outputs(args, results, data, str(out), names)
+        return out
+
+    plain = save('plain', '-v', '0')
+    assert listed(plain) == []
+    alone = {flag: save(flag[1:], flag, '-v', '0')
+        for flag in POSTERIOR_FLAGS}
+    capsys.readouterr()
+    every = save('every', *POSTERIOR_FLAGS, '-v', '1')
+    printed = capsys.readouterr().out.splitlines()
+
+    union = set(os.listdir(plain))
+    for flag, out in alone.items():
+        new = set(os.listdir(out)) - set(os.listdir(plain))
+        assert len(new) == FILES_PER_FLAG[flag], flag
+        assert not new & union, flag
+        union |= new
+        assert listed(out) == [POSTERIOR_FLAGS[flag]]
+        for name in os.listdir(out):
+            if name != 'args.txt':
+                assert (out / name).read_bytes() \
+                    == (every / name).read_bytes(), (flag, name)
+    assert set(os.listdir(every)) == union
+    assert listed(every) == list(POSTERIOR_FLAGS.values())
+    assert 'posterior_doublets: 0.05\n' in (every / 'args.txt').read_text()
+    # `posterior: <n> clusters ...` is the estimator's own line
+    assert [ln.split(':')[0] for ln in printed
+        if ln.startswith('posterior ')] == SUMMARY_LINES
