@@ -474,9 +474,11 @@ def fast_paths():
     out.update(hostkernels.probe())
     out['native_mh'] = _native_kernels() is not None
     out['native_beta'] = bool(_native_beta())
-    out['native_moves'] = bool(_native_moves_allowed()) \
+    # (no native move is made without the native Beta sampler: _native_move)
+    out['native_moves'] = out['native_beta'] \
+        and bool(_native_moves_allowed()) \
         and _lib.env('BNPC_NATIVE_MOVES', '1') != '0'
-    out['native_step'] = out['native_moves'] and out['native_beta'] \
+    out['native_step'] = out['native_moves'] \
         and bool(_native_step_allowed()) \
         and _lib.env('BNPC_NATIVE_STEP', '1') != '0'
     return out
