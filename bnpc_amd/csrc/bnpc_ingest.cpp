@@ -5,8 +5,13 @@
 // Semantics restated from /root/reference/libs/dpmmIO.py:27-98: entries are
 // 0 | 1 | 2 | 3 (possibly written as floats), separated by ONE separator
 // character (space, tab or comma); an empty field or 3 is "missing"; 2
-// (homozygous) counts as 1.  Separator / header-row / index-column sniffing
-// stays in Python (bnpc_amd/io.py); this file only scans the body.
+// (homozygous) counts as 1.  Lines are what pandas.read_csv, the reader the
+// reference rests on, takes for lines: one that is empty or holds only spaces
+// and tabs that do not separate is skipped wherever it stands, every other
+// line is a row (a lone separator: a row of missing entries), no line is
+// stripped, and a line with more fields than the first one is refused.
+// Separator / header-row / index-column sniffing stays in Python
+// (bnpc_amd/io.py); this file only scans the body.
 // Output codes: 0, 1, 3 (missing) as int8, row-major in FILE orientation.
 
 #include <errno.h>
@@ -40,10 +45,18 @@ static int read_all(const char *path, std::vector<char> &buf)
     return 0;
 }
 
+static inline bool is_blank(char ch)
+{
+    return ch == ' ' || ch == '\t' || ch == '\r';
+}
+
+// [b, e) lies inside the file's buffer, which ends with the sentinel newline:
+// a number of any length is converted where it stands (strtod stops at the
+// separator, the line's end or the sentinel at the latest).
 static inline int token_code(const char *b, const char *e, int *code)
 {
-    while (b < e && (*b == ' ' || *b == '\r')) b++;
-    while (e > b && (e[-1] == ' ' || e[-1] == '\r')) e--;
+    while (b < e && is_blank(*b)) b++;
+    while (e > b && is_blank(e[-1])) e--;
     if (b == e) {
         *code = 3;
         return 0;
@@ -51,14 +64,14 @@ static inline int token_code(const char *b, const char *e, int *code)
     if (e - b == 1 && *b >= '0' && *b <= '3') {
         *code = *b - '0';
     } else {
-        char tmp[64];
-        const size_t n = (size_t)(e - b);
-        if (n >= sizeof(tmp)) return 1;
-        memcpy(tmp, b, n);
-        tmp[n] = 0;
+        // decimal spellings only (strtod alone would take hexadecimal ones)
+        for (const char *q = b; q < e; q++)
+            if (!((*q >= '0' && *q <= '9') || *q == '.' || *q == '+'
+                  || *q == '-' || *q == 'e' || *q == 'E'))
+                return 1;
         char *end = nullptr;
-        const double v = strtod(tmp, &end);
-        if (end == tmp || *end != 0) return 1;
+        const double v = strtod(b, &end);
+        if (end != e) return 1;
         if (v == 0.0) *code = 0;
         else if (v == 1.0) *code = 1;
         else if (v == 2.0) *code = 2;
@@ -82,30 +95,53 @@ extern "C" int bnpc_parse_matrix(const char *path, char sep, int skip_rows,
     std::vector<char> buf;
     if (read_all(path, buf)) return 1;
     const char *p = buf.data();
-    const char *end = p + buf.size();
-    // drop trailing blank lines
-    const char *last = end - 1;
-    while (last > p && (last[-1] == '\n' || last[-1] == '\r' ||
-                        last[-1] == ' ')) last--;
-    for (int s = 0; s < skip_rows && p < last; s++) {
-        while (p < last && *p != '\n') p++;
-        p++;
-    }
+    const char *end = p + buf.size();   // end[-1] is the sentinel newline
     int64_t r = 0, width = 0;
     const int64_t want_cols = out ? *cols : 0;
-    while (p < last) {
+    // fields a line may hold (the index column counted): those of the first
+    // line that is one, and one more where named rows stand under a header
+    // that names the columns only - a longer line is refused, as read_csv
+    // refuses it ("Expected .. fields, saw ..")
+    int64_t allowed = -1;
+    int to_skip = skip_rows;
+    for (; p < end; ) {
         const char *eol = p;
         while (*eol != '\n') eol++;
+        const char *line = p;
+        p = eol + 1;
         const char *le = eol;
-        if (le > p && le[-1] == '\r') le--;
-        if (sep == ' ') {           // the Python reader strips the line
-            while (p < le && *p == ' ') p++;
-            while (le > p && le[-1] == ' ') le--;
+        if (le > line && le[-1] == '\r') le--;
+        // read_csv's skip_blank_lines: a line is no row (and no header) if
+        // it is empty or holds only spaces and tabs that do not separate
+        bool blank = true;
+        int64_t fields = 1;
+        for (const char *q = line; q < le; q++) {
+            if (*q == sep) fields++;
+            if (*q == sep || (*q != ' ' && *q != '\t')) blank = false;
+        }
+        if (blank) continue;
+        if (to_skip > 0) {
+            to_skip--;
+            allowed = fields;
+            continue;
+        }
+        if (allowed < 0 || (r == 0 && skip_rows && skip_index
+                            && fields == allowed + 1))
+            allowed = fields;
+        if (fields > allowed) {
+            bnpc_set_error("row %lld holds %lld fields, the lines before it "
+                           "%lld", (long long)r, (long long)fields,
+                           (long long)allowed);
+            return 3;
+        }
+        if (out && r >= *rows) {            // more rows than the first pass saw
+            r++;
+            break;
         }
         int64_t c = 0;
-        const char *tok = p;
+        const char *tok = line;
         bool first = true;
-        for (const char *q = p;; q++) {
+        for (const char *q = line;; q++) {
             if (q == le || *q == sep) {
                 if (!(first && skip_index)) {
                     if (out) {
@@ -130,7 +166,6 @@ extern "C" int bnpc_parse_matrix(const char *path, char sep, int skip_rows,
                 out[r * want_cols + j] = 3;      // ragged row: missing
         if (c > width) width = c;
         r++;
-        p = eol + 1;
     }
     if (out && (r != *rows || width > want_cols)) {
         bnpc_set_error("matrix shape changed between passes");

@@ -43,20 +43,30 @@ def _sniff_layout(head):
     return sep, header_row, index_col
 
 
+def _sniff_head(lines, in_file):
+    """What the layout is sniffed from: the first five lines, stripped, the
+    blank ones left out."""
+    head = [ln.strip() for ln in lines[:5] if ln.strip()]
+    if not head:
+        raise ValueError(f'Could not read data from file: {in_file}')
+    return head
+
+
+def _is_blank(line, sep):
+    """pandas.read_csv's skip_blank_lines, the reader the reference rests on:
+    a line is no row (and no header) if it is empty or holds only spaces and
+    tabs that do not separate."""
+    return all(ch in ' \t' and ch != sep for ch in line)
+
+
 def load_codes_native(in_file, transpose=True):
     """The same matrix as `load_data`, as int8 codes 0 | 1 | 3 (missing),
     cells x mutations, scanned by libbnpc_hip.so's byte scanner
     (bnpc_parse_matrix).  No names."""
     import ctypes as C
     from bnpc_amd import _lib
-    head = []
     with open(in_file, 'r') as f:
-        for _ in range(5):
-            ln = f.readline()
-            if ln.strip():
-                head.append(ln.strip())
-    if not head:
-        raise ValueError(f'Could not read data from file: {in_file}')
+        head = _sniff_head([f.readline() for _ in range(5)], in_file)
     sep, header_row, index_col = _sniff_layout(head)
     lib = _lib.load()
     rows, cols = C.c_int64(0), C.c_int64(0)
@@ -64,6 +74,8 @@ def load_codes_native(in_file, transpose=True):
     bsep = sep.encode()
     _lib.check(lib.bnpc_parse_matrix(path, bsep, int(header_row),
         int(index_col), None, C.byref(rows), C.byref(cols)), 'parse_matrix')
+    if rows.value < 1 or cols.value < 1:
+        raise ValueError(f'Could not read data from file: {in_file}')
     codes = np.empty((rows.value, cols.value), dtype=np.int8)
     _lib.check(lib.bnpc_parse_matrix(path, bsep, int(header_row),
         int(index_col), _lib.ptr(codes, C.c_int8), C.byref(rows),
@@ -94,24 +106,30 @@ def load_data(in_file, transpose=True, get_names=False):
     """
     with open(in_file, 'r') as f:
         lines = [ln.rstrip('\r\n') for ln in f]
-    while lines and lines[-1].strip() == '':
-        lines.pop()
+    sep, header_row, index_col = _sniff_layout(_sniff_head(lines, in_file))
+    # the lines are read_csv's: blank ones are skipped wherever they stand,
+    # every other line is a row (a lone separator: a row of missing
+    # entries), no line is stripped, and one with more fields than the first
+    # is refused (bnpc_parse_matrix reads the same way)
+    lines = [ln for ln in lines if not _is_blank(ln, sep)]
+
+    col_names, allowed = None, None
+    if header_row:
+        col_names = lines[0].strip().split(sep)
+        allowed = len(lines[0].split(sep))
+        lines = lines[1:]
     if not lines:
         raise ValueError(f'Could not read data from file: {in_file}')
 
-    sep, header_row, index_col = _sniff_layout(
-        [ln.strip() for ln in lines[:5]])
-
-    col_names = None
-    if header_row:
-        col_names = lines[0].strip().split(sep)
-        lines = lines[1:]
-
     rows, row_names = [], []
     for ln in lines:
-        toks = ln.strip('\r\n').split(sep)
-        if sep == ' ':
-            toks = ln.strip().split(sep)
+        toks = ln.split(sep)
+        if allowed is None or (not rows and header_row and index_col
+                and len(toks) == allowed + 1):
+            allowed = len(toks)
+        if len(toks) > allowed:
+            raise ValueError(f'{in_file}: row {len(rows)} holds {len(toks)} '
+                f'fields, the lines before it {allowed}')
         if index_col:
             row_names.append(toks[0])
             toks = toks[1:]

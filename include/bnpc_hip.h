@@ -956,6 +956,10 @@ int bnpc_gamma_logpdf_scalar(const bnpc_host_kernels *k, double x, double a,
  * Body scanner for the reference's text matrix format (libs/dpmmIO.py:27-98):
  * fields 0|1|2|3 (2 -> 1; 3 or empty -> missing) separated by `sep`.  Skips
  * `skip_rows` header lines and, if skip_index, the first field of each line.
+ * Lines are pandas.read_csv's: an empty line, or one of spaces and tabs that
+ * do not separate, is skipped wherever it stands; a line of separators alone
+ * is a row of missing entries; nothing is stripped; a line with more fields
+ * than the first one is refused (code 3), a shorter one is padded.
  * Call once with out == NULL to get rows/cols, then with an int8 buffer of
  * rows*cols (file orientation; codes 0, 1, 3).  Host only, no GPU. */
 int bnpc_parse_matrix(const char *path, char sep, int skip_rows,

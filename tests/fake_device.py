@@ -12,9 +12,38 @@ from bnpc_amd import _lib
 
 class FakeContext:
     def __init__(self, data=None, codes=None, device=0):
-        self.data = np.asarray(data, dtype=np.float64)
+        """The three creation routes of _lib.Context with their refusals (a
+        RuntimeError, as _lib.check raises): a BitPlanes matrix (no bit in
+        both planes, none past M), int8 codes 0 | 1 | 2 | 3 (2 reads as 1),
+        float64 holding 0, 1 or NaN."""
+        planes = getattr(data, 'planes', None)
+        if planes is not None:
+            N, M = data.shape
+            words = np.asarray(planes, dtype='<u8')
+            tail = np.uint64((1 << (M - 64 * ((M - 1) // 64))) - 1
+                if M % 64 else 2 ** 64 - 1)
+            if N > 0 and M > 0 and ((words[:, :, 0] & words[:, :, 1]).any()
+                    or ((words[:, -1, 0] | words[:, -1, 1]) & ~tail).any()):
+                raise RuntimeError('bit planes are inconsistent')
+            full = np.asarray(data, dtype=np.float64).reshape(N, M) \
+                if N > 0 and M > 0 else np.empty((N, M))
+        elif codes is not None:
+            codes = np.asarray(codes, dtype=np.int8)
+            if ((codes < 0) | (codes > 3)).any():
+                raise RuntimeError('codes are not 0, 1, 2, 3')
+            full = np.where(codes == 3, np.nan,
+                np.where(codes == 2, 1, codes)).astype(np.float64)
+        else:
+            full = np.asarray(data, dtype=np.float64)
+            if not (np.isnan(full) | (full == 0) | (full == 1)).all():
+                raise RuntimeError('data is not 0, 1 or missing')
+        self.data = full
         self.N, self.M = self.data.shape
-        self.views = {0: np.arange(self.N)}
+        if self.N < 1 or self.M < 1:
+            raise RuntimeError('N and M must be positive')
+        self.views = {v: np.zeros(0, dtype=np.int64)
+            for v in range(1, _lib.MAX_VIEWS)}
+        self.views[0] = np.arange(self.N)
         self.lab = None
         self.calls = {}
 
@@ -30,7 +59,13 @@ class FakeContext:
 
     def view_set(self, view, cells):
         self._count('view_set')
-        self.views[view] = np.asarray(cells, dtype=np.int64).copy()
+        cells = np.asarray(cells, dtype=np.int64).copy()
+        # refused before anything changes, as bnpc_view_set refuses
+        if not 1 <= view < _lib.MAX_VIEWS:
+            raise RuntimeError('view out of range')
+        if ((cells < 0) | (cells >= self.N)).any():
+            raise RuntimeError('cell index out of range')
+        self.views[view] = cells
         return self.views[view].size
 
     def view_set_slot(self, view, cells, slot):
@@ -177,6 +212,10 @@ class FakeContext:
         labels = np.asarray(labels)
         cells = self.views[view]
         assert labels.size == cells.size
+        if not 0 < G <= 4096:
+            raise RuntimeError('G out of range')
+        if (labels >= G).any():
+            raise RuntimeError('segment label out of range')
         n1, n0 = self.colcounts([cells[labels == g] for g in range(G)])
         self.calls['colcounts'] -= 1
         return n1, n0
@@ -187,6 +226,11 @@ class FakeContext:
     def colcounts_by_label(self, assignment, ids, fetch=True):
         self._count('colcounts_by_label')
         assignment = np.asarray(assignment)
+        ids = np.asarray(ids, dtype=np.int64)
+        if ids.size < 1 or (ids < 0).any() \
+                or np.unique(ids).size != ids.size \
+                or not np.isin(assignment, ids).all():
+            raise RuntimeError('ids or assignment refused')
         segs = [np.flatnonzero(assignment == i) for i in ids]
         n1, n0 = self.colcounts(segs)
         self.lab = (n1, n0)
