@@ -44,6 +44,10 @@ CELL_TILE = 8       # bnpc_post_passes.hip: CG_CELLS (cells per workgroup)
 MUT_FIT_ROWS = 32   # bnpc_post_passes.hip: MF_ROWS (cluster rows of a wave's LDS tile)
 DOUBLET_TILE = 8    # bnpc_post_passes.hip: DB_TILE (candidates of a wave of k_db_sums)
 DOUBLET_UNROLL = 2  # bnpc_post_passes.hip: DB_UNROLL (mutations per trip of its loop)
+ORDER_TILE = 64     # bnpc_post_passes.hip: PO_TILE (mutations along a side of a pair tile)
+ORDER_STAGE = 16    # bnpc_post_passes.hip: PO_STAGE (mask rows of a tile side in LDS)
+ORDER_LDS_ROWS = 8192   # bnpc_post_passes.hip: PO_LDS_ROWS (rows whose sizes sit in LDS)
+ORDER_WG = 1024     # bnpc_post_passes.hip: PO_WG (workgroups of k_po_live, rows of k_po_masks)
 
 _i64 = C.c_int64
 # array arguments travel as plain addresses (building a typed ctypes pointer
@@ -337,6 +341,10 @@ SIGNATURES = {
     'bnpc_post_place_times': (C.c_int, [C.c_void_p, C.c_void_p, _i64, _i64,
         _pi32, _i64, _pf, _i64, _pd, _pd, _pd, C.c_double, C.c_double, _i64,
         _i64, C.POINTER(C.c_float)]),
+    'bnpc_post_mutation_order': (C.c_int, [C.c_void_p, _pf, _i64, _i64, _i64,
+        _i64, _i64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'bnpc_post_mutation_order_times': (C.c_int, [C.c_void_p, _pf, _i64, _i64,
+        _i64, _i64, _i64, C.POINTER(C.c_float)]),
     'bnpc_post_chain_agreement': (C.c_int, [C.c_void_p, _pi64, _i64, _pi64,
         _pi64, _pi64]),
     'bnpc_post_chain_agreement_times': (C.c_int, [C.c_void_p, _pi64, _i64,
@@ -1075,6 +1083,39 @@ class Posterior:
             codes.shape[0], codes.shape[1], ptr(labels), K, ptr(par),
             par.shape[1], ptr(FN), ptr(FP), ptr(alpha), mix1, mix0,
             int(chunk), int(slab), ms), 'post_place_times')
+        return tuple(x / 1e3 for x in ms)
+
+    def mutation_order(self, params, min_cells=2, chunk=0, slab=0,
+            want=(True, True, True, True)):
+        """The relation of every pair of mutations counted over the posterior
+        (bnpc_post_mutation_order) -> (anc, same, excl, conf), each (M, M)
+        uint32, the integers of postproc.host_mutation_order: anc[a][b] the
+        samples in which a is strictly ancestral to b, same / excl / conf
+        those in which the two are carried by the same live clusters, by
+        disjoint ones, or break the three-gamete rule.  params: the samples x
+        W x M trace; min_cells: the cells a cluster needs to count as live;
+        chunk: samples on the device at a time (0: about 512 MB); slab: the
+        rows a whose table rows are resident at a time (0: what the free
+        device memory takes).  The same bits for any chunk and slab.  want: a
+        table that is not wanted is not fetched and comes back as None."""
+        par = self._trace(params)
+        M = par.shape[2]
+        out = [np.empty((M, M), dtype=np.uint32) if w else None for w in want]
+        check(load().bnpc_post_mutation_order(self._h, ptr(par), par.shape[1],
+            M, int(min_cells), int(chunk), int(slab),
+            *[None if o is None else ptr(o) for o in out]),
+            'post_mutation_order')
+        return tuple(out)
+
+    def mutation_order_times(self, params, min_cells=2, chunk=0, slab=0):
+        """Seconds by device events, summed over one mutation_order call
+        that brings no table back: (trace uploads, ranks and live rows, mask
+        kernel, pair kernel)."""
+        par = self._trace(params)
+        ms = (C.c_float * 4)()
+        check(load().bnpc_post_mutation_order_times(self._h, ptr(par),
+            par.shape[1], par.shape[2], int(min_cells), int(chunk), int(slab),
+            ms), 'post_mutation_order_times')
         return tuple(x / 1e3 for x in ms)
 
     def chain_agreement(self, bounds):

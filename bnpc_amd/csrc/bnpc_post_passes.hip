@@ -1,7 +1,8 @@
 // bnpc_post_passes.hip - the posterior passes that walk the parameter trace
 // or the data behind a bnpc_post handle: the cluster genotypes, and per cell
-// or per mutation the genotypes (-pg), the fit (-pf, -pm) and the doublet
-// scores (-pd).  The passes over the labels and the pair counts alone are in
+// or per mutation the genotypes (-pg), the fit (-pf, -pm), the doublet
+// scores (-pd), the placement of held-out cells and the ordering of every pair
+// of mutations (-po).  The passes over the labels and the pair counts alone are in
 // bnpc_codist.hip; the pieces every driver here is made of in bnpc_post.h.
 //
 // Every kernel here is launched from this file only (k_cg_rank and k_mf_masks
@@ -2525,4 +2526,385 @@ extern "C" int bnpc_post_place_times(bnpc_post *p, const uint8_t *codes,
     const PnOut out = {};
     return pn_run(p, codes, Q, M, labels, K, params, W, FN, FP, alpha, mix1,
                   mix0, chunk, slab, out, ms);
+}
+
+// ---------------------------------------------------------------------------
+// Posterior ordering of every pair of mutations (-po): in every sample each
+// live cluster (a row r < D_s whose label has min_cells cells or more) has a
+// called genotype, P[s][r][m] > 0.5f, so mutation m is a set A_m of live rows
+// and two mutations stand in one relation under the three-gamete rule - from
+//   x11 = A_a and A_b meet, x10 = A_a \ A_b not empty, x01 = A_b \ A_a not empty
+// same (x11 only), a ancestral to b (x11, x10), b ancestral to a (x11, x01),
+// exclusive (x10, x01), conflict (all three), else absent.  anc, same, excl,
+// conf count the samples per ordered pair, uint32 M x M;
+// postproc.host_mutation_order is the host loop this is pinned to.
+//
+// Per slab of table rows a and chunk of samples:
+// k_cg_rank    all N cells' ranks in the chunk's samples
+// k_po_live    workgroup = sample: the sizes of its rows by integer atomics
+//              (LDS up to PO_LDS_ROWS rows, past that a global slice per
+//              workgroup), then the live rows as ceil(W / 64) 64-bit words
+// k_po_masks   thread = mutation, a launch row per (sample, word): the bits of
+//              the word's live rows r < D_s with P > 0.5f.  masks[sample]
+//              [word][M]: the lanes run along the mutations for the trace's
+//              loads, the mask's store and the pair kernel's loads alike
+// k_po_pairs   workgroup = tile of PO_TILE x PO_TILE pairs, thread = PO_BLOCK
+//              a x PO_BLOCK b of them with their counters in registers over
+//              the whole chunk.  PO_STAGE mask rows of the tile's a and b side
+//              go through LDS at a time (16 KiB); a thread reads its a masks
+//              as 16-byte pieces (the same address in 16 lanes) and its b
+//              masks at stride 16, so that the lanes of an 8-byte read lie
+//              side by side.  The three any-bits come from and / and-not of
+//              the words; the five counters take sums of their products - no
+//              branch.  With one word a sample (W <= 64) a mask row is a
+//              sample; with more the any-bits of the words met so far are
+//              kept packed per pair until the sample's last word.  Where the
+//              slab holds all M rows only the tiles on and above the diagonal
+//              run, and a tile writes anc[b][a] (its fifth counter) and the
+//              mirrored same, excl, conf as well.  The tables are read at the
+//              kernel's start and written at its end: no atomics.
+// ---------------------------------------------------------------------------
+#define PO_TILE 64                  // mutations along a side of a tile
+#define PO_BLOCK 4                  // a thread's pairs: PO_BLOCK a x PO_BLOCK b
+#define PO_STAGE 16                 // mask rows of a tile side in LDS at a time
+#define PO_LDS_ROWS 8192            // rows whose sizes k_po_live keeps in LDS
+#define PO_WG 1024                  // workgroups of k_po_live, launch rows of k_po_masks
+
+// one chunk of sc samples: rank its [sc][N] rows; live [sc][ww]
+template <bool GLOBAL>
+__global__ __launch_bounds__(256) void k_po_live(
+    const unsigned short *__restrict__ rank, long long N, int sc, int W,
+    int ww, long long min_cells, int *gsizes,
+    unsigned long long *__restrict__ live)
+{
+    extern __shared__ int po_sizes[];
+    int *sizes = GLOBAL ? gsizes + (size_t)blockIdx.x * W : po_sizes;
+    const int tid = threadIdx.x;
+    for (int q = blockIdx.x; q < sc; q += gridDim.x) {
+        for (int r = tid; r < W; r += 256) {
+            if (GLOBAL)
+                __hip_atomic_store(sizes + r, 0, __ATOMIC_RELAXED,
+                                   __HIP_MEMORY_SCOPE_AGENT);
+            else
+                sizes[r] = 0;
+        }
+        if (GLOBAL) __threadfence();
+        __syncthreads();
+        const unsigned short *rk = rank + (size_t)q * N;
+        for (long long i = tid; i < N; i += 256) atomicAdd(&sizes[rk[i]], 1);
+        if (GLOBAL) __threadfence();
+        __syncthreads();
+        for (int w = tid; w < ww; w += 256) {
+            const int r0 = w * 64, r1 = min(W, r0 + 64);
+            unsigned long long bits = 0;
+            for (int r = r0; r < r1; r++) {
+                const int n = GLOBAL
+                    ? __hip_atomic_load(sizes + r, __ATOMIC_RELAXED,
+                                        __HIP_MEMORY_SCOPE_AGENT)
+                    : sizes[r];
+                bits |= (unsigned long long)((long long)n >= min_cells)
+                    << (r - r0);
+            }
+            live[(size_t)q * ww + w] = bits;
+        }
+        __syncthreads();                    // the sizes are reused
+    }
+}
+
+// one chunk of sc samples: P its [sc][W][M] trace, distinct / live the
+// chunk's; masks [sc * ww][M]
+__global__ __launch_bounds__(256) void k_po_masks(
+    const float *__restrict__ P, int sc, int W, int ww, long long M,
+    const int *__restrict__ distinct,
+    const unsigned long long *__restrict__ live,
+    unsigned long long *__restrict__ masks)
+{
+    const long long m = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (m >= M) return;
+    const long long units = (long long)sc * ww;
+    for (long long u = blockIdx.y; u < units; u += gridDim.y) {
+        const int q = (int)(u / ww), w = (int)(u - (long long)q * ww);
+        const int r0 = w * 64, r1 = min(distinct[q], r0 + 64);
+        const unsigned long long lv = live[u];
+        const float *col = P + ((size_t)q * W + r0) * M + m;
+        unsigned long long bits = 0;
+        // (the word's live bits are the same in every lane)
+        for (int r = r0; r < r1; r++, col += M)
+            if ((lv >> (r - r0)) & 1)
+                bits |= (unsigned long long)(*col > 0.5f) << (r - r0);
+        masks[(size_t)u * M + m] = bits;
+    }
+}
+
+// masks: `units` rows of M, ww of them a sample (ONE: ww == 1).  The tables
+// are the slab's [na][M], its rows the mutations a0 .. a0 + na; SYM: a0 == 0,
+// na == M, and the tiles below the diagonal leave at once
+template <bool ONE, bool SYM>
+__global__ __launch_bounds__(256) void k_po_pairs(
+    const unsigned long long *__restrict__ masks, long long units, int ww,
+    long long M, long long a0, long long na, unsigned *anc, unsigned *same,
+    unsigned *excl, unsigned *conf)
+{
+    __shared__ __attribute__((aligned(16)))
+        unsigned long long sa[PO_STAGE][PO_TILE];
+    __shared__ __attribute__((aligned(16)))
+        unsigned long long sb[PO_STAGE][PO_TILE];
+    if (SYM && blockIdx.x < blockIdx.y) return;
+    const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
+    const long long at = a0 + (long long)blockIdx.y * PO_TILE;
+    const long long bt = (long long)blockIdx.x * PO_TILE;
+    const long long a_end = a0 + na;
+    unsigned c_anc[PO_BLOCK][PO_BLOCK], c_desc[PO_BLOCK][PO_BLOCK],
+        c_same[PO_BLOCK][PO_BLOCK], c_excl[PO_BLOCK][PO_BLOCK],
+        c_conf[PO_BLOCK][PO_BLOCK], any[PO_BLOCK][PO_BLOCK];
+#pragma unroll
+    for (int i = 0; i < PO_BLOCK; i++) {
+#pragma unroll
+        for (int j = 0; j < PO_BLOCK; j++) {
+            const long long a = at + ty * PO_BLOCK + i, b = bt + tx + 16 * j;
+            const bool in = a < a_end && b < M;
+            const size_t idx = in ? (size_t)(a - a0) * M + b : 0;
+            c_anc[i][j] = in ? anc[idx] : 0u;
+            c_same[i][j] = in ? same[idx] : 0u;
+            c_excl[i][j] = in ? excl[idx] : 0u;
+            c_conf[i][j] = in ? conf[idx] : 0u;
+            c_desc[i][j] = SYM && in ? anc[(size_t)b * M + a] : 0u;
+            any[i][j] = 0u;
+        }
+    }
+    int w = 0;
+    for (long long u0 = 0; u0 < units; u0 += PO_STAGE) {
+        const int nu = (int)min((long long)PO_STAGE, units - u0);
+        __syncthreads();                    // the last rows have been read
+        for (int e = tid; e < nu * PO_TILE; e += 256) {
+            const int k = e >> 6, c = e & 63;
+            const unsigned long long *row = masks + (size_t)(u0 + k) * M;
+            sa[k][c] = at + c < M ? row[at + c] : 0ull;
+            sb[k][c] = bt + c < M ? row[bt + c] : 0ull;
+        }
+        __syncthreads();
+        for (int k = 0; k < nu; k++) {
+            unsigned long long va[PO_BLOCK], vb[PO_BLOCK];
+            const ulonglong2 *pa = (const ulonglong2 *)&sa[k][ty * PO_BLOCK];
+#pragma unroll
+            for (int i = 0; i < PO_BLOCK; i += 2) {
+                const ulonglong2 t = pa[i >> 1];
+                va[i] = t.x;
+                va[i + 1] = t.y;
+            }
+#pragma unroll
+            for (int j = 0; j < PO_BLOCK; j++) vb[j] = sb[k][tx + 16 * j];
+            const bool last = ONE || w == ww - 1;   // (the same in every lane)
+#pragma unroll
+            for (int i = 0; i < PO_BLOCK; i++) {
+#pragma unroll
+                for (int j = 0; j < PO_BLOCK; j++) {
+                    unsigned x11 = (va[i] & vb[j]) != 0ull;
+                    unsigned x10 = (va[i] & ~vb[j]) != 0ull;
+                    unsigned x01 = (vb[j] & ~va[i]) != 0ull;
+                    if (!ONE) {
+                        any[i][j] |= x11 | (x10 << 1) | (x01 << 2);
+                        if (!last) continue;
+                        x11 = any[i][j] & 1u;
+                        x10 = (any[i][j] >> 1) & 1u;
+                        x01 = any[i][j] >> 2;
+                        any[i][j] = 0u;
+                    }
+                    const unsigned both = x11 & x10, only = x11 & (x10 ^ 1u);
+                    const unsigned n01 = x01 ^ 1u;
+                    c_conf[i][j] += both & x01;
+                    c_anc[i][j] += both & n01;
+                    c_desc[i][j] += only & x01;
+                    c_same[i][j] += only & n01;
+                    c_excl[i][j] += (x11 ^ 1u) & x10 & x01;
+                }
+            }
+            if (!ONE) w = w + 1 == ww ? 0 : w + 1;
+        }
+    }
+    const bool mirror = SYM && blockIdx.x != blockIdx.y;
+#pragma unroll
+    for (int i = 0; i < PO_BLOCK; i++) {
+#pragma unroll
+        for (int j = 0; j < PO_BLOCK; j++) {
+            const long long a = at + ty * PO_BLOCK + i, b = bt + tx + 16 * j;
+            if (a >= a_end || b >= M) continue;
+            const size_t idx = (size_t)(a - a0) * M + b;
+            anc[idx] = c_anc[i][j];
+            same[idx] = c_same[i][j];
+            excl[idx] = c_excl[i][j];
+            conf[idx] = c_conf[i][j];
+            if (mirror) {
+                const size_t back = (size_t)b * M + a;
+                anc[back] = c_desc[i][j];
+                same[back] = c_same[i][j];
+                excl[back] = c_excl[i][j];
+                conf[back] = c_conf[i][j];
+            }
+        }
+    }
+}
+
+// ms (NULL, or 4 floats): device-event milliseconds summed over the call -
+// ms[0] the trace uploads, ms[1] k_cg_rank and k_po_live, ms[2] k_po_masks,
+// ms[3] k_po_pairs (with its tables' zeroing)
+static int po_run(bnpc_post *p, const float *params, int64_t W, int64_t M,
+                  int64_t min_cells, int64_t chunk, int64_t slab,
+                  uint32_t *anc, uint32_t *same, uint32_t *excl,
+                  uint32_t *conf, float *ms)
+{
+    if (!p || !params || min_cells < 1 || W < 1 || W >= (int64_t)GT_MIXED
+        || M < 1 || M > (int64_t)65535 * PO_TILE || chunk < 0 || slab < 0) {
+        bnpc_set_error("bad argument: the mutation order needs min_cells >= 1, "
+                       "a 1 <= W < 65534 x 1 <= M <= 65535 * 64 trace, chunk "
+                       ">= 0 and slab >= 0");
+        return 2;
+    }
+    const char *const pass = "mutation order";
+    if (int rc = post_check_handle(pass, p)) return rc;
+    const int64_t S = p->S, N = p->N;
+    PCK(hipSetDevice(p->device));
+    PostBuffers buf;
+    PostLaps laps;
+    PostArea area;
+    int *d_distinct;
+    if (int rc = post_check_distinct(pass, p, W, buf, area, &d_distinct))
+        return rc;
+
+    // the chunk of samples: its trace, its masks, its ranks and live rows (a
+    // launch counts its mask rows as an int), then as many table rows as fit
+    // beside it
+    const int64_t ww = (W + 63) / 64;
+    const size_t sample_floats = (size_t)W * M;
+    int64_t sc = post_default_chunk(chunk, sample_floats * sizeof(float)
+                                    + (size_t)ww * M * 8 + (size_t)N * 2
+                                    + (size_t)ww * 8, S);
+    sc = std::min<int64_t>(sc, std::max<int64_t>(1, ((int64_t)1 << 30) / ww));
+    const bool in_lds = W <= PO_LDS_ROWS;
+    const unsigned live_grid = (unsigned)std::min<int64_t>(sc, PO_WG);
+    float *d_P;
+    unsigned short *d_rank;
+    unsigned long long *d_live, *d_masks;
+    int *d_sizes = nullptr;
+    POST_ALLOC(buf, pass, &d_P, (size_t)sc * sample_floats);
+    POST_ALLOC(buf, pass, &d_rank, (size_t)sc * N);
+    POST_ALLOC(buf, pass, &d_live, (size_t)sc * ww);
+    POST_ALLOC(buf, pass, &d_masks, (size_t)sc * ww * M);
+    if (!in_lds) POST_ALLOC(buf, pass, &d_sizes, (size_t)live_grid * W);
+    size_t free_b = 0, total_b = 0;
+    PCK(hipMemGetInfo(&free_b, &total_b));
+    const size_t per_row = (size_t)M * 16;
+    const size_t margin = (size_t)64 << 20;
+    const size_t room = free_b > margin ? (free_b - margin) / per_row : 0;
+    const int64_t na = slab ? std::min(slab, M)
+                            : (int64_t)std::min<size_t>((size_t)M, room);
+    if (na < 1 || (size_t)na > room) {
+        bnpc_set_error("mutation order: a slab of %lld x %lld pairs needs "
+                       "%.1f GB, %.1f GB of device memory are free",
+                       (long long)std::max<int64_t>(na, 1), (long long)M,
+                       (double)std::max<int64_t>(na, 1) * per_row / 1e9,
+                       free_b / 1e9);
+        return 5;
+    }
+    unsigned *d_tab[4];
+    uint32_t *const host[4] = {anc, same, excl, conf};
+    for (int t = 0; t < 4; t++)
+        POST_ALLOC(buf, pass, &d_tab[t], (size_t)na * M);
+    PCK(laps.start(ms, 4));
+    const bool sym = na >= M, one = ww == 1, one_chunk = sc >= S;
+    const unsigned tiles_b = (unsigned)((M + PO_TILE - 1) / PO_TILE);
+    for (int64_t a0 = 0; a0 < M; a0 += na) {
+        const int64_t rows = std::min(na, M - a0);
+        laps.begin();
+        for (int t = 0; t < 4; t++)
+            PCK(hipMemset(d_tab[t], 0, (size_t)rows * M * sizeof(unsigned)));
+        laps.end(3);
+        for (int64_t s0 = 0; s0 < S; s0 += sc) {
+            const int64_t n = std::min(sc, S - s0);
+            const int64_t units = n * ww;
+            if (!one_chunk || a0 == 0) {
+                laps.begin();
+                PCK(hipMemcpy(d_P, params + (size_t)s0 * sample_floats,
+                              (size_t)n * sample_floats * sizeof(float),
+                              hipMemcpyHostToDevice));
+                laps.end(0);
+                laps.begin();
+                post_launch_rank(p, area, s0, n, 0, N, N, d_rank);
+                PCK(hipGetLastError());
+                const dim3 lg((unsigned)std::min<int64_t>(n, live_grid));
+                if (in_lds)
+                    hipLaunchKernelGGL(k_po_live<false>, lg, dim3(256),
+                                       (size_t)W * sizeof(int), 0, d_rank,
+                                       (long long)N, (int)n, (int)W, (int)ww,
+                                       (long long)min_cells, (int *)nullptr,
+                                       d_live);
+                else
+                    hipLaunchKernelGGL(k_po_live<true>, lg, dim3(256), 0, 0,
+                                       d_rank, (long long)N, (int)n, (int)W,
+                                       (int)ww, (long long)min_cells, d_sizes,
+                                       d_live);
+                PCK(hipGetLastError());
+                laps.end(1);
+                laps.begin();
+                hipLaunchKernelGGL(k_po_masks,
+                                   dim3((unsigned)((M + 255) / 256),
+                                        (unsigned)std::min<int64_t>(units,
+                                                                    PO_WG)),
+                                   dim3(256), 0, 0, d_P, (int)n, (int)W,
+                                   (int)ww, (long long)M, d_distinct + s0,
+                                   d_live, d_masks);
+                PCK(hipGetLastError());
+                laps.end(2);
+            }
+            laps.begin();
+            const dim3 grid(tiles_b,
+                            (unsigned)((rows + PO_TILE - 1) / PO_TILE));
+#define PO_LAUNCH(ONE_, SYM_)                                                \
+            hipLaunchKernelGGL((k_po_pairs<ONE_, SYM_>), grid, dim3(256), 0,  \
+                               0, d_masks, (long long)units, (int)ww,        \
+                               (long long)M, (long long)a0, (long long)rows, \
+                               d_tab[0], d_tab[1], d_tab[2], d_tab[3])
+            if (one && sym) PO_LAUNCH(true, true);
+            else if (one) PO_LAUNCH(true, false);
+            else if (sym) PO_LAUNCH(false, true);
+            else PO_LAUNCH(false, false);
+#undef PO_LAUNCH
+            PCK(hipGetLastError());
+            laps.end(3);
+        }
+        for (int t = 0; t < 4; t++)
+            if (host[t])
+                PCK(hipMemcpy(host[t] + (size_t)a0 * M, d_tab[t],
+                              (size_t)rows * M * sizeof(unsigned),
+                              hipMemcpyDeviceToHost));
+    }
+    PCK(hipDeviceSynchronize());
+    return laps.result(pass);
+}
+
+extern "C" int bnpc_post_mutation_order(bnpc_post *p, const float *params,
+                                        int64_t W, int64_t M,
+                                        int64_t min_cells, int64_t chunk,
+                                        int64_t slab, uint32_t *anc,
+                                        uint32_t *same, uint32_t *excl,
+                                        uint32_t *conf)
+{
+    return po_run(p, params, W, M, min_cells, chunk, slab, anc, same, excl,
+                  conf, nullptr);
+}
+
+// diagnostic (tools/posterior_bench.py): one bnpc_post_mutation_order call
+// without its tables' way back, by device events (see po_run)
+extern "C" int bnpc_post_mutation_order_times(bnpc_post *p,
+                                              const float *params, int64_t W,
+                                              int64_t M, int64_t min_cells,
+                                              int64_t chunk, int64_t slab,
+                                              float *ms)
+{
+    if (!ms) {
+        bnpc_set_error("bad argument: NULL");
+        return 2;
+    }
+    return po_run(p, params, W, M, min_cells, chunk, slab, nullptr, nullptr,
+                  nullptr, nullptr, ms);
 }

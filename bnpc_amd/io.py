@@ -527,6 +527,73 @@ def save_placement(out_dir, chain, est, tables, assignment, names=None):
     return paths
 
 
+# the most mutations whose pairs save_mutation_order lists one by one
+# (M (M - 1) / 2 lines: half a million at the limit)
+MUTATION_PAIRS_MAX = 1000
+
+
+def save_mutation_order(out_dir, chain, est, tables, names=None):
+    """The -po files of postproc.mutation_order for one (chain, estimator)
+    row.  mutation_order_<est>_<chain>.tsv: per mutation its name (`names`,
+    the loader's mutation names, when there is one per mutation, else
+    0..M-1), `carried`, `depth`, `parent` (a name, or `root`), `p_parent`,
+    `same_as` (a name, or `-`), `n_same`, `n_descendants`, `n_exclusive`,
+    `conflict`, `worst_conflict` (a name, or `-`), `p_worst_conflict`; floats
+    %.4f.  mutation_order_summary_<est>_<chain>.txt: `key: value` lines -
+    samples, mutations, pairs, min_cells, the shares of the pairs that are
+    ancestral, same, exclusive, conflict, absent or undecided, mean_conflict,
+    roots, max_depth, skipped_ancestors, most_conflicting (name:value pairs)
+    and pairs_table (`written`, or `skipped` above MUTATION_PAIRS_MAX
+    mutations).  mutation_pairs_<est>_<chain>.tsv, up to that limit: every
+    pair a < b with `p_anc` (a ancestral to b), `p_desc` (b to a), `p_same`,
+    `p_excl`, `p_conflict`."""
+    M = tables['carried'].size
+    index = _row_names(names, M).tolist()
+    paths = _paths(out_dir, ('mutation_order.tsv',
+        'mutation_order_summary.txt', 'mutation_pairs.tsv'), est, chain)
+    columns = ('carried', 'depth', 'parent', 'p_parent', 'same_as', 'n_same',
+        'n_descendants', 'n_exclusive', 'conflict', 'worst_conflict',
+        'p_worst_conflict')
+    named = {'parent': 'root', 'same_as': '-', 'worst_conflict': '-'}
+    whole = ('depth', 'n_same', 'n_descendants', 'n_exclusive')
+
+    def cell(key, val):
+        if key in named:
+            return str(index[int(val)]) if val >= 0 else named[key]
+        return str(int(val)) if key in whole else f'{val:.4f}'
+    with open(paths[0], 'w') as f:
+        f.write('mutation\t' + '\t'.join(columns) + '\n')
+        for m, name in enumerate(index):
+            f.write(f'{name}\t'
+                + '\t'.join(cell(k, tables[k][m]) for k in columns) + '\n')
+    total = tables['total']
+    S = total['samples']
+    listed = M <= MUTATION_PAIRS_MAX
+    with open(paths[1], 'w') as f:
+        for key in ('samples', 'mutations', 'pairs', 'min_cells'):
+            f.write(f'{key}: {total[key]}\n')
+        for key in ('ancestral', 'same', 'exclusive', 'conflict', 'absent',
+                'undecided', 'mean_conflict'):
+            f.write(f'{key}: {total[key]:.4f}\n')
+        for key in ('roots', 'max_depth', 'skipped_ancestors'):
+            f.write(f'{key}: {total[key]}\n')
+        f.write('most_conflicting: ' + _name_values(index,
+            tables['conflict'], total['most_conflicting']) + '\n')
+        f.write(f'pairs_table: {"written" if listed else "skipped"}\n')
+    if not listed:
+        return paths[:2]
+    anc, same, excl, conf = (tables[k] for k in ('anc', 'same', 'excl',
+        'conf'))
+    with open(paths[2], 'w') as f:
+        f.write('a\tb\tp_anc\tp_desc\tp_same\tp_excl\tp_conflict\n')
+        for a in range(M):
+            for b in range(a + 1, M):
+                f.write(f'{index[a]}\t{index[b]}\t' + '\t'.join(
+                    f'{int(t[a, b]) / S:.4f}'
+                    for t in (anc, anc.T, same, excl, conf)) + '\n')
+    return paths
+
+
 def save_chain_agreement(out_dir, chain, est, tables, names=None):
     """The -pc files of postproc.chain_agreement for one (chain, estimator)
     row.  chain_agreement_<est>_<chain>.tsv: per cell its name (`names`, the

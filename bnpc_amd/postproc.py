@@ -35,6 +35,11 @@ The -pc tables (every chain's co-clustering against that of the other chains
 pooled - not a reference output) are one more pass of the pair-count tile loop
 over the samples, chain by chain (bnpc_post_chain_agreement;
 host_chain_agreement is the host loop it is pinned to).
+The -po tables (the relation of every pair of mutations under the
+three-gamete rule, counted over the samples, and the mutation forest they
+imply - not a reference output) are a device pass over the samples and the
+parameter trace, on cluster bit masks (bnpc_post_mutation_order;
+host_mutation_order is the host loop it is pinned to).
 The -tc / -td metrics (V-measure, ARI, Hamming; utils.py:49-72) are
 restated from integer counts at the end; tree helpers are out of scope.
 """
@@ -405,7 +410,7 @@ def concat_chain_results(results):
 
 
 def posterior_estimate(results, data, support=False, cells=False, fit=False,
-        mutations=False, doublets=False, chains=False):
+        mutations=False, doublets=False, chains=False, ordering=False):
     """`-e posterior` (the default estimator), chains pooled
     (utils.py:195-244).  support=True: the key 'support' holds the tables of
     cluster_support for the MPEAR clustering, made from the pair counts of
@@ -421,7 +426,9 @@ def posterior_estimate(results, data, support=False, cells=False, fit=False,
     the posterior means of the error rates on the same handle.  chains=True:
     the key 'chains' holds the tables of chain_agreement, every chain's
     samples against the other chains', with the bounds of results_bounds, on
-    the same handle."""
+    the same handle.  ordering: a cluster size of 1 or more (min_cells) adds
+    the key 'mutation_order' with the tables of mutation_order, from the
+    samples and their parameter trace on the same handle."""
     res = concat_chain_results(results)
     tables = {}
     if doublets:
@@ -430,7 +437,7 @@ def posterior_estimate(results, data, support=False, cells=False, fit=False,
                 params, np.mean(res['FN']), np.mean(res['FP']), doublets)
     else:
         with_genotypes = None
-    if support or cells or fit or mutations or chains:
+    if support or cells or fit or mutations or chains or ordering:
         def while_open(post, assign):
             if support:
                 tables['support'] = posterior_support(post, assign)
@@ -447,6 +454,9 @@ def posterior_estimate(results, data, support=False, cells=False, fit=False,
                 tables['mutation_fit'] = mutation_fit(post, data,
                     res['assignments'], res['params'], res['FN'], res['FP'],
                     order=assign)
+            if ordering:
+                tables['mutation_order'] = mutation_order(post,
+                    res['assignments'], res['params'], int(ordering))
     else:
         while_open = None
     assign, params = _mean_hierarchy(res['assignments'], res['params'],
@@ -590,6 +600,142 @@ def cell_genotypes(post, assignments, params_full):
     mean = sum1 / S
     sd = np.sqrt(np.maximum(sum2 / S - mean * mean, 0))
     return {'mean': mean, 'sd': sd, 'prob': ones / S}
+
+
+# ---------------------------------------------------------------------------
+# posterior ordering of every pair of mutations (-po): which mutation came
+# first, which share a branch, which sit on separate lineages - the relation
+# of the two under the three-gamete rule in every posterior sample, counted;
+# not a reference output, so the definition below is the specification
+# ---------------------------------------------------------------------------
+def host_mutation_order(assignments, params_full, min_cells=2):
+    """(anc, same, excl, conf), each (M, M) uint32: the samples in which the
+    pair of mutations (a, b) stands in each relation.  In sample s the
+    distinct labels in increasing order are the rows r < D_s of
+    params_full[s] (rows >= D_s are padding, never read); row r is live iff
+    its label has at least min_cells cells; A_m is the set of live rows with
+    the float32 params_full[s][r][m] > 0.5 (0.5 itself and NaN are not
+    carried).  With x11 = A_a and A_b meet, x10 = A_a minus A_b is not empty,
+    x01 = A_b minus A_a is not empty: same is x11 alone, anc[a][b] (a strictly
+    ancestral to b) x11 and x10, anc[b][a] x11 and x01, excl x10 and x01,
+    conf all three; any other case (a or b carried by no live row) counts
+    nowhere.  The plain loop bnpc_post_mutation_order is pinned to."""
+    assignments = np.asarray(assignments)
+    min_cells = int(min_cells)
+    if min_cells < 1:
+        raise ValueError('min_cells must be 1 or more')
+    S = assignments.shape[0]
+    M = params_full.shape[2]
+    tables = [np.zeros((M, M), dtype=np.uint32) for _ in range(4)]
+    anc, same, excl, conf = tables
+    for s in range(S):
+        sizes = np.unique(assignments[s], return_counts=True)[1]
+        rows = np.asarray(params_full[s][:sizes.size], dtype=np.float32)
+        with np.errstate(invalid='ignore'):
+            g = (rows > np.float32(0.5))[sizes >= min_cells]
+        # (counts of rows, below 2 ** 24: exact in float32)
+        g = g.astype(np.float32)
+        n11 = g.T @ g
+        n10 = g.T @ (1 - g)
+        x11, x10, x01 = n11 > 0, n10 > 0, n10.T > 0
+        same += x11 & ~x10 & ~x01
+        anc += x11 & x10 & ~x01
+        excl += ~x11 & x10 & x01
+        conf += x11 & x10 & x01
+    return anc, same, excl, conf
+
+
+def mutation_order(post, assignments, params_full, min_cells=2):
+    """The -po tables.  'anc', 'same', 'excl', 'conf': the (M, M) uint32
+    counts of host_mutation_order - from the device pass
+    (Posterior.mutation_order) where the open clustering handle has one, else
+    from the host loop.  From them, with S the samples and p = count / S, per
+    mutation m (arrays of M):
+      carried            same[m][m] / S: the share of the samples that carry m
+      depth              |Anc(m)|, Anc(m) = {b != m: anc[b][m] > S / 2}
+      n_descendants      |{b: anc[m][b] > S / 2}|
+      parent, p_parent   the b of Anc(m) with depth(b) < depth(m) that has the
+                         largest depth (ties: the larger anc[b][m], then the
+                         smaller index) and anc[b][m] / S; -1 and 0 for a
+                         root.  The strict depth makes the parents a forest
+                         even where the majorities are not transitive
+      skipped_ancestors  the members of Anc(m) that condition excludes
+      same_as            the smallest b < m with same[b][m] > S / 2, else -1
+      n_same,            the b != m whose same / excl exceeds S / 2
+      n_exclusive
+      conflict           the mean over b != m of conf[m][b] / S (0 for M = 1)
+      worst_conflict,    the b with the largest conf[m][b] (ties: the smaller
+      p_worst_conflict   index) and conf[m][b] / S; -1 and 0 if all are 0
+    and 'total': samples, mutations, pairs, min_cells; the shares of the
+    M (M - 1) / 2 pairs whose relation has p > 0.5 - ancestral (either way),
+    same, exclusive, conflict, absent - and undecided, the rest;
+    mean_conflict, roots, max_depth, skipped_ancestors (summed) and
+    most_conflicting, the ten mutations with the largest conflict (ties: the
+    smaller index)."""
+    assignments = np.asarray(assignments)
+    S = int(assignments.shape[0])
+    min_cells = int(min_cells)
+    device = getattr(post, 'mutation_order', None)
+    if device is not None:
+        anc, same, excl, conf = device(params_full, min_cells)
+    else:
+        anc, same, excl, conf = host_mutation_order(assignments, params_full,
+            min_cells)
+    M = anc.shape[0]
+    idx = np.arange(M)
+    off = ~np.eye(M, dtype=bool)
+    # count > S / 2 in integers
+    major = lambda t: (2 * t.astype(np.int64) > S) & off
+    anc_of = major(anc).T                   # anc_of[m][b]: b in Anc(m)
+    depth = anc_of.sum(axis=1)
+    parent = np.full(M, -1, dtype=np.int64)
+    p_parent = np.zeros(M)
+    skipped = np.zeros(M, dtype=np.int64)
+    for m in range(M):
+        cand = np.flatnonzero(anc_of[m])
+        ok = cand[depth[cand] < depth[m]]
+        skipped[m] = cand.size - ok.size
+        if ok.size:
+            best = min(ok.tolist(),
+                key=lambda b: (-depth[b], -int(anc[b, m]), b))
+            parent[m] = best
+            p_parent[m] = anc[best, m] / S
+    same_major = major(same)
+    same_as = np.full(M, -1, dtype=np.int64)
+    for m in range(M):
+        below = np.flatnonzero(same_major[m, :m])
+        if below.size:
+            same_as[m] = below[0]
+    conf_off = np.where(off, conf, 0).astype(np.int64)
+    conflict = conf_off.sum(axis=1) / S / (M - 1) if M > 1 else np.zeros(M)
+    worst = np.argmax(conf_off, axis=1).astype(np.int64)   # first maximum
+    worst_n = conf_off[idx, worst]
+    worst[worst_n == 0] = -1
+    upper = np.triu(np.ones((M, M), dtype=bool), 1)
+    pairs = M * (M - 1) // 2
+    absent = S - (anc.astype(np.int64) + anc.T + same + excl + conf)
+
+    def share(mask):
+        return float((mask & upper).sum() / pairs) if pairs else 0.0
+    shares = {'ancestral': share(major(anc) | major(anc).T),
+        'same': share(same_major), 'exclusive': share(major(excl)),
+        'conflict': share(major(conf)), 'absent': share(major(absent))}
+    top = sorted(range(M), key=lambda m: (-conflict[m], m))[:10]
+    total = {'samples': S, 'mutations': M, 'pairs': pairs,
+        'min_cells': min_cells, **shares,
+        'undecided': (1.0 - sum(shares.values())) if pairs else 0.0,
+        'mean_conflict': float(conflict.mean()),
+        'roots': int((parent < 0).sum()), 'max_depth': int(depth.max()),
+        'skipped_ancestors': int(skipped.sum()), 'most_conflicting': top}
+    return {'anc': anc, 'same': same, 'excl': excl, 'conf': conf,
+        'carried': same[idx, idx] / S, 'depth': depth.astype(np.int64),
+        'n_descendants': major(anc).sum(axis=1).astype(np.int64),
+        'parent': parent, 'p_parent': p_parent,
+        'skipped_ancestors': skipped, 'same_as': same_as,
+        'n_same': same_major.sum(axis=1).astype(np.int64),
+        'n_exclusive': major(excl).sum(axis=1).astype(np.int64),
+        'conflict': conflict, 'worst_conflict': worst,
+        'p_worst_conflict': worst_n / S, 'total': total}
 
 
 # ---------------------------------------------------------------------------

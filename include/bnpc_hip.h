@@ -1280,6 +1280,44 @@ int bnpc_post_place_times(bnpc_post *post, const uint8_t *codes, int64_t Q,
                           const float *params, int64_t W, const double *FN,
                           const double *FP, const double *alpha, double mix1,
                           double mix0, int64_t chunk, int64_t slab, float *ms);
+/* Posterior ordering of every pair of mutations (-po; not a reference output):
+ * which of two mutations came first, under the three-gamete rule of a perfect
+ * phylogeny, counted over the post's samples.  params: the S x W x M float32
+ * trace.  In sample s the distinct labels in increasing order are the rows
+ * r < D_s of params[s] (rows >= D_s are padding and never read); row r is live
+ * iff its label has at least min_cells cells in the sample; A_m is the set of
+ * live rows with params[s][r][m] > 0.5f (exactly 0.5 and NaN are not carried).
+ * For the pair (a, b), with x11 = A_a and A_b meet, x10 = A_a \ A_b is not
+ * empty, x01 = A_b \ A_a is not empty, the sample counts into
+ *   same[a][b]  x11, not x10, not x01
+ *   anc[a][b]   x11, x10, not x01 (a strictly ancestral to b; b ancestral to
+ *               a counts into anc[b][a])
+ *   excl[a][b]  not x11, x10, x01
+ *   conf[a][b]  x11, x10, x01
+ * and into none of them otherwise (a or b is carried by no live row).  The
+ * four tables are M x M uint32, row-major; same, excl and conf are symmetric,
+ * same[m][m] the samples that carry m at all, the other diagonals 0
+ * (bnpc_amd.postproc.host_mutation_order is the definition).  chunk: the
+ * samples whose trace and row masks are on the device at a time (0: about 512
+ * MB); slab: the rows a whose four table rows are on the device at a time (0:
+ * as many as the free device memory takes; where that is all M, every
+ * unordered tile of pairs is visited once).  Integers only and no atomics on
+ * the tables: every output has the same bits for any chunk and slab, on every
+ * call; each may be NULL.  Return code 2, and no output written, for
+ * min_cells < 1, W outside [1, 65534), M < 1 (or M > 65535 * 64), sample
+ * labels outside [0, N) or a sample with more than W clusters; 5 if the slab
+ * does not fit the device's free memory. */
+int bnpc_post_mutation_order(bnpc_post *post, const float *params, int64_t W,
+                             int64_t M, int64_t min_cells, int64_t chunk,
+                             int64_t slab, uint32_t *anc, uint32_t *same,
+                             uint32_t *excl, uint32_t *conf /* M x M each */);
+/* diagnostic: one bnpc_post_mutation_order call without its tables' way back,
+ * milliseconds by device events summed over the call - ms[0] the uploads,
+ * ms[1] the ranks and the live rows, ms[2] the mask kernel, ms[3] the pair
+ * kernel */
+int bnpc_post_mutation_order_times(bnpc_post *post, const float *params,
+                                   int64_t W, int64_t M, int64_t min_cells,
+                                   int64_t chunk, int64_t slab, float *ms);
 /* Between-chain agreement of the clustering (-pc; not a reference output): is
  * one chain's co-clustering that of the others?  The post's samples are the
  * chains' pooled samples, chain after chain; bounds (C + 1 int64, 0 = b_0 <

@@ -33,7 +33,13 @@ doublets_posterior_mean.tsv, doublet_summary_posterior_mean.txt;
 -pc (not a reference flag either) compares every chain's co-clustering with
 that of the other chains pooled - did the chains find the same clustering?
 (needs -n 2 or more): chain_agreement_posterior_mean.tsv,
-chain_summary_posterior_mean.txt.
+chain_summary_posterior_mean.txt;
+-po [MIN] (not a reference flag either) relates every pair of mutations - is
+one nested in the other, are they carried by the same clusters, by disjoint
+ones, or do they break a perfect phylogeny? - counted over the posterior
+samples on clusters of MIN (2) cells or more: mutation_order_posterior_mean.tsv,
+mutation_order_summary_posterior_mean.txt, mutation_pairs_posterior_mean.tsv
+(up to 1000 mutations).
 """
 import argparse
 from datetime import datetime
@@ -47,6 +53,14 @@ def _ratio(val):
     if val <= 0 or val >= 1:
         raise argparse.ArgumentTypeError(
             f'Invalid value: {val}. Values need to be 0 < x < 1')
+    return val
+
+
+def _min_cells(val):
+    val = int(val)
+    if val < 1:
+        raise argparse.ArgumentTypeError(
+            f'Invalid value: {val}. Values need to be 1 or more')
     return val
 
 
@@ -173,6 +187,16 @@ FLAGS = [
         'the two sides call differently: a chain that stands out has not '
         'mixed (needs -e posterior and -n 2 or more; one more pass over '
         'samples x pairs of cells on the GPU).')),
+    ('output', '-po', '--posterior_order', dict(type=_min_cells, nargs='?',
+        const=2, default=argparse.SUPPRESS, metavar='MIN', help='Relate every '
+        'pair of mutations under the three-gamete rule in every posterior '
+        'sample - one nested in the other, on the same clusters, on disjoint '
+        'clusters, or in conflict with a perfect phylogeny - and write the '
+        'probabilities, the mutation forest they imply and how often every '
+        'mutation breaks the phylogeny; a cluster counts from MIN cells '
+        '(default 2: a transient one-cell cluster is ignored; 1 is the '
+        'strict reading) (needs -e posterior; one more pass over samples x '
+        'pairs of mutations on the GPU).')),
 ]
 
 
@@ -185,6 +209,7 @@ class Args(argparse.Namespace):
     posterior_mutations = False
     posterior_doublets = False
     posterior_chains = False
+    posterior_order = False
 
 
 def build_parser():
@@ -234,6 +259,10 @@ def check_args(args):
         raise SystemExit('-pd / --posterior_doublets writes tables of the '
             'posterior samples: it needs `posterior` among the estimators '
             f'(-e), which are: {" ".join(ests)}')
+    if getattr(args, 'posterior_order', False) and 'posterior' not in ests:
+        raise SystemExit('-po / --posterior_order writes tables of the '
+            'posterior samples: it needs `posterior` among the estimators '
+            f'(-e), which are: {" ".join(ests)}')
     if getattr(args, 'posterior_chains', False):
         if 'posterior' not in ests:
             raise SystemExit('-pc / --posterior_chains writes tables of the '
@@ -267,7 +296,8 @@ def save_outputs(args, results, data, out_dir, names=None):
                 fit=getattr(args, 'posterior_fit', False),
                 mutations=getattr(args, 'posterior_mutations', False),
                 doublets=getattr(args, 'posterior_doublets', False),
-                chains=getattr(args, 'posterior_chains', False))
+                chains=getattr(args, 'posterior_chains', False),
+                ordering=getattr(args, 'posterior_order', False))
             rows_a.append(('mean', est,
                 ' '.join(str(i) for i in inf['assignment'])))
             inferred.append(('mean', est, inf))
@@ -301,6 +331,11 @@ def save_outputs(args, results, data, out_dir, names=None):
                         f'{total["worst_chain"]} '
                         f'({total["worst_mean_diff"]:.4f}), flip share '
                         f'{total["flip_share"]:.4f}')
+                if 'mutation_order' in inf:
+                    total = inf['mutation_order']['total']
+                    print(f'posterior order: {total["roots"]} roots, depth '
+                        f'{total["max_depth"]}, conflict share '
+                        f'{total["conflict"]:.4f}')
             continue
         for chain, res in chains:
             res = res if res is not None else postproc.best_chain(results, est)
@@ -329,7 +364,8 @@ def save_outputs(args, results, data, out_dir, names=None):
                 val = [f'{t:%Y%m%d_%H:%M:%S}' for t in val]
             if key in ('posterior_support', 'posterior_genotypes',
                     'posterior_fit', 'posterior_mutations',
-                    'posterior_doublets', 'posterior_chains') and not val:
+                    'posterior_doublets', 'posterior_chains',
+                    'posterior_order') and not val:
                 continue        # listed only when it is set
             f.write(f'{key}: {val}\n')
     mut_names = names[1] if names is not None else None
@@ -354,6 +390,9 @@ def save_outputs(args, results, data, out_dir, names=None):
         if 'chains' in inf:
             bio.save_chain_agreement(out_dir, chain, est, inf['chains'],
                 names[0] if names is not None else None)
+        if 'mutation_order' in inf:
+            bio.save_mutation_order(out_dir, chain, est,
+                inf['mutation_order'], mut_names)
     # the metric tables list their rows chain by chain, as the reference
     # does (its per-chain dictionary, dpmmIO.py:524-530); the pooled
     # posterior first

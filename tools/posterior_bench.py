@@ -68,7 +68,21 @@ per second of k_db_sums - then the call with its results brought to the host,
 then k_db_sums of the doublet pass at the same new cells and the nearest
 number of candidates, its scores per second and the ratio of the two; with
 PLACE_HOST=<samples>,<new cells> the host loop (postproc.host_place) and the
-device on that many of both; then exit."""
+device on that many of both; then exit.
+ORDER=1: right after the pair counts are made, the mutation-order pass
+(bnpc_post_mutation_order) of ORDER_M (default 1000) mutations against a
+random float32 trace of ORDER_W (default C + 8) rows per sample - every row a
+random subset of the mutations, so that all relations occur - with ORDER_MIN
+(default 2) cells a live cluster, ORDER_CHUNK samples and ORDER_SLAB table rows
+at a time (0: the defaults): ORDER_REPS (default 5) calls by device events
+(Posterior.mutation_order_times) - the fastest one's uploads, ranks and live
+rows, k_po_masks and k_po_pairs, the pair-samples per second of k_po_pairs
+(the unordered pairs with the diagonal where one slab holds all rows, else all
+ordered pairs) and their share of the device's 32-bit vector issue rate at the
+24 vector instructions a pair-sample costs in the one-word kernel - then the
+call with its four tables brought to the host; with ORDER_HOST=<samples> the
+host loop (postproc.host_mutation_order) and the device on that many samples,
+compared; then exit."""
 import os
 import sys
 import time
@@ -197,6 +211,58 @@ if os.environ.get('DOUBLETS') == '1':
             '; max |ll_pair dev - host| =',
             float(np.abs(got[3] - want['ll_pair']).max()))
     post.close()
+    sys.exit(0)
+if os.environ.get('ORDER') == '1':
+    # 32-bit vector instructions per second, per lane: 256 compute units x 4
+    # SIMDs x 32 lanes at 2.4 GHz
+    INT_OPS = 256 * 4 * 32 * 2.4e9
+    PAIR_OPS = 24       # of the one-word k_po_pairs, counted in its ISA
+    M = int(os.environ.get('ORDER_M', '1000'))
+    W = int(os.environ.get('ORDER_W', str(C + 8)))
+    min_cells = int(os.environ.get('ORDER_MIN', '2'))
+    chunk = int(os.environ.get('ORDER_CHUNK', '0'))
+    slab = int(os.environ.get('ORDER_SLAB', '0'))
+    reps = int(os.environ.get('ORDER_REPS', '5'))
+    params = np.empty((S, W, M), dtype=np.float32)
+    rate = rng.random_sample(M) ** 2
+    for s in range(S):
+        params[s] = np.where(rng.random_sample((W, M)) < rate, 0.9, 0.1)
+    sym = slab == 0 or slab >= M
+    pairs = M * (M + 1) // 2 if sym else M * M
+    print(f'mutation order: M={M} W={W} ({(W + 63) // 64} mask words) '
+        f'min_cells={min_cells} chunk={chunk} slab={slab}, trace '
+        f'{params.nbytes / 1e9:.2f} GB, tables {16 * M * M / 1e9:.2f} GB, '
+        f'{S * pairs:.3e} pair-samples')
+    runs = []
+    for r in range(reps):
+        t = post.mutation_order_times(params, min_cells, chunk, slab)
+        runs.append((sum(t),) + t)
+        print(f'  rep {r}: uploads {t[0] * 1e3:.3f} ms  k_cg_rank + k_po_live '
+            f'{t[1] * 1e3:.3f} ms  k_po_masks {t[2] * 1e3:.3f} ms  k_po_pairs '
+            f'{t[3] * 1e3:.3f} ms', flush=True)
+    total, _, _, _, t_pairs = min(runs)
+    t_pairs = min(r[4] for r in runs)
+    print(f'  fastest of {reps} (device events): pass {total * 1e3:.3f} ms; '
+        f'k_po_pairs {t_pairs * 1e3:.3f} ms = {S * pairs / t_pairs:.3e} '
+        f'pair-samples/s, {PAIR_OPS * S * pairs / t_pairs / INT_OPS:.1%} of '
+        f'the 32-bit vector issue rate {INT_OPS:.3e}/s', flush=True)
+    t0 = time.perf_counter()
+    got = post.mutation_order(params, min_cells, chunk, slab)
+    t0 = lap('Posterior.mutation_order (call, four tables to the host)', t0)
+    post.close()
+    if os.environ.get('ORDER_HOST'):
+        Sh = int(os.environ['ORDER_HOST'])
+        t0 = time.perf_counter()
+        want = postproc.host_mutation_order(a[:Sh], params[:Sh], min_cells)
+        t0 = lap(f'host loop (postproc.host_mutation_order) at S={Sh}', t0)
+        small = _lib.Posterior(a[:Sh])
+        t0 = time.perf_counter()
+        have = small.mutation_order(params[:Sh], min_cells, chunk, slab)
+        t0 = lap(f'Posterior.mutation_order at S={Sh}', t0)
+        small.close()
+        print('  device == host:', all(np.array_equal(g, w)
+            for g, w in zip(have, want)), '; counted:',
+            [int(w.astype(np.int64).sum()) for w in want])
     sys.exit(0)
 if os.environ.get('PLACE') == '1':
     M = int(os.environ.get('PLACE_M', '1000'))
